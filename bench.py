@@ -4,10 +4,16 @@
 Workload (BASELINE.json configs[2]): PMSM dq-frame, explicit Euler, fp32, batch 2^22 per GPU,
 tau = 1e-4. One bench "step" = one vmap_sim_ahead launch of `--chunk` (default 100) solver steps over the whole
 batch with full reference outputs (observations + all physical-state trajectories); chunks are chained through
-last_state, so the default 100 timed steps are the 10 000-step run. Inputs (initial state, one action chunk that
-every step reuses) are resident in HBM before the timed region.
+last_state, so the default 100 timed steps are the 10 000-step run: the timed region starts again from the seeded initial
+state, whatever the set-up and warm-up steps before it did. Inputs (initial state, one action chunk that every step reuses)
+are resident in HBM before the timed region and the same from run to run for the same arguments.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line. `--dump-outputs DIR` also writes what the timed
+path returned in its last step (a fixed, seeded sample of the environments) as DIR/<name>.npy. `--full` adds what takes
+runs of its own: the in-run rocprofv3 traffic passes (before the GPU is touched), the same-run placement calibration after
+the timed region and the CPU-oracle baseline.
 
 N > 1: one rank per GPU, batch sharded (weak scaling: 2^22 envs per rank), no collective on the stepping path. Either
 launched by torch.distributed.run (WORLD_SIZE / RANK / LOCAL_RANK in the environment) or invoked directly — then this
@@ -350,6 +356,14 @@ def parse_args():
                          "N > 0 (sim_ahead path, lane-major trajectories): allocate N output-buffer sets during set-up, keep the "
                          "one a probe launch runs fastest into (physical placement moves the kernel by up to 25 %%, DESIGN.md "
                          "§6) and write it again every step (vmap_sim_ahead(out=...))")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: roofline.traffic by rocprofv3 --pmc child passes, the same-run "
+                         "placement calibration and the CPU-oracle baseline (each can be left out again with its --no-* option); "
+                         "a plain run replays profiles/traffic.json for roofline.traffic")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the timed path returned in its last step as DIR/<name>.npy (float32 / "
+                         "float64): observations, state trajectories and last state of a fixed, seeded sample of the environments, "
+                         "at most 64 MB in all")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-live-traffic", action="store_true",
@@ -357,7 +371,40 @@ def parse_args():
                          "~20 s); the committed passes of profiles/traffic.json are replayed instead")
     ap.add_argument("--no-calibration", action="store_true", help="skip the same-run placement calibration after the timed region")
     ap.add_argument("--no-pool", action="store_true", help="every step allocates its outputs (no pooled sets, no placement check)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.dump_outputs is not None and args.steps < 1:
+        ap.error("--dump-outputs needs at least one timed step")
+    return args
+
+
+DUMP_BYTES = 60_000_000  # --dump-outputs: array bytes in all (the .npy headers stay far inside 64 MB)
+DUMP_MAX_ENVS = 4096
+DUMP_SEED = 20241016
+
+
+def dump_outputs(out_dir, outputs, B):
+    """Writes the timed path's last outputs as out_dir/<name>.npy: every [B, ...] array of `outputs` (name -> tensor; the tiled
+    layout's [B/T, T, ...] views count as [B, ...]) restricted to the same sorted, seeded sample of environments (all of them
+    when B is small enough), in the arrays' own precision. The sample depends only on B and on the sizes of the arrays, so two
+    builds run with the same arguments write comparable files."""
+    outputs = {k: v for k, v in outputs.items() if v is not None}
+    per_env = sum(v.numel() // B * v.element_size() for v in outputs.values())
+    n = max(1, min(B, DUMP_MAX_ENVS, DUMP_BYTES // max(per_env, 1)))
+    idx = np.arange(B) if n == B else np.sort(np.random.default_rng(DUMP_SEED).choice(B, size=n, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for name, t in outputs.items():
+        assert t.dtype in (torch.float32, torch.float64), (name, t.dtype)
+        it = torch.as_tensor(idx, device=t.device)
+        if t.shape[0] == B:
+            sel = t[it]
+        else:  # tiled: [B/T, T, ...]
+            assert t.ndim >= 2 and t.shape[0] * t.shape[1] == B, (name, tuple(t.shape))
+            sel = t[it // t.shape[1], it % t.shape[1]]
+        sel = sel.cpu().numpy()
+        np.save(os.path.join(out_dir, f"{name}.npy"), sel)
+        written[name] = list(sel.shape)
+    return {"dir": out_dir, "envs": int(n), "seed": DUMP_SEED, "arrays": written}
 
 
 def launch_ranks(args):
@@ -394,9 +441,9 @@ def main():
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if world != args.gpus:
         sys.exit(f"bench.py: WORLD_SIZE={world} does not match --gpus {args.gpus}")
-    live_traffic = (None, "not requested")
-    # the full default line only (quick A/B runs pass --no-cpu-baseline and skip this too); BEFORE anything here touches the GPU
-    if world == 1 and not args.no_live_traffic and not args.no_cpu_baseline:
+    live_traffic = (None, "measured only with --full")
+    # --full only (quick A/B runs pass --no-cpu-baseline and skip this too); BEFORE anything here touches the GPU
+    if args.full and world == 1 and not args.no_live_traffic and not args.no_cpu_baseline:
         live_traffic = measure_traffic_live(args)
     assert torch.cuda.is_available(), "bench.py needs a HIP device"
     # rehearsal knobs (single-GPU box): EXCENV_BENCH_ONE_GPU=1 puts every rank on GPU 0, EXCENV_BENCH_BACKEND=gloo
@@ -417,6 +464,10 @@ def main():
     from exciting_environments_amd.distributed import ObservationGatherer
 
     env, state, actions, B, Kc, reg, solver, dtype = build_env(args, device, rank)
+    # the timed region starts from this snapshot: how many set-up / settle steps ran before it depends on timing (placement)
+    from exciting_environments_amd.tree import tree_map
+
+    state0 = tree_map(lambda t: t.clone() if torch.is_tensor(t) else t, state)
     if args.vec or args.lds_pad:
         env.launch_opts = _native.launch_opts(envs_per_lane=args.vec, lds_pad_bytes=args.lds_pad)
     use_gather = args.gather != "none" and (world > 1 or os.environ.get("EXCENV_BENCH_FORCE_GATHER") == "1")
@@ -438,6 +489,14 @@ def main():
     step_actions = [actions[:, k, :].contiguous() for k in range(min(Kc, 8))] if args.path == "step" else None
     step_count = [0]
     last_obs = [None]
+    last_out = [None]  # what the last step returned, name -> tensor (--dump-outputs)
+
+    def named_outputs(obs, states, last):
+        named = {"observations": obs}
+        if states is not None:
+            named.update({f"states.physical_state.{n}": getattr(states.physical_state, n) for n in env.STATE_FIELDS})
+        named.update({f"last_state.physical_state.{n}": getattr(last.physical_state, n) for n in env.STATE_FIELDS})
+        return named
 
     def final_row(obs):
         if obs.ndim == 2:
@@ -450,6 +509,7 @@ def main():
             obs, last = env.vmap_step(st, step_actions[step_count[0] % len(step_actions)])
             step_count[0] += 1
             last_obs[0] = obs
+            last_out[0] = (obs, None, last)
             return last
         nonlocal bufs
         if bufs is not None:
@@ -458,6 +518,7 @@ def main():
         else:
             obs, states, last = env.vmap_sim_ahead(st, actions, env.tau, env.tau)
         last_obs[0] = obs
+        last_out[0] = (obs, states, last)
         if gatherer is not None and args.gather == "chunk":
             gatherer.wait()  # previous chunk's gather must have drained before its buffer is reused
             gathered = gatherer.start(final_row(obs), gathered)
@@ -483,6 +544,8 @@ def main():
             state = one_step(state)
         gathered = gatherer.start(final_row(last_obs[0]), gathered)
         gatherer.wait()
+    state = tree_map(lambda t: t.clone() if torch.is_tensor(t) else t, state0)
+    del state0
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -524,6 +587,10 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
+    dumped = None
+    if args.dump_outputs is not None and rank == 0:  # rank 0 writes its own shard
+        dumped = dump_outputs(args.dump_outputs, named_outputs(*last_out[0]), B)
+    last_out[0] = None
     finite = bool(torch.isfinite(state.physical_state.__dict__[env.STATE_FIELDS[-1]]).all())
     gather_ok = None
     if gathered is not None and last_obs[0] is not None:  # this rank's slice of the gathered batch is its own final row
@@ -567,7 +634,7 @@ def main():
             traffic = None
 
     calib = None
-    if rank == 0 and not args.no_calibration:
+    if args.full and rank == 0 and not args.no_calibration:
         calib = calibrate_placement(env, state, actions, args, Kc, B, dtype)
     if rank == 0:
         total_steps = B * world * Kc * args.steps
@@ -642,7 +709,9 @@ def main():
         # the ingredients of a weak-scaling comparison; the efficiency itself is the driver's to compute from per-N values
         out["value_at_median_rank_kernel"] = B * world * Kc / (med_rank * 1e-3) if args.steps else None
         out["value_at_slowest_rank_kernel"] = B * world * Kc / (slow_rank * 1e-3) if args.steps else None
-        if world == 1 and not args.no_cpu_baseline:
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args, reg, solver, dtype, env.tau, Kc)
         print(json.dumps(out), flush=True)
     if dist.is_initialized():

@@ -3,31 +3,32 @@
 # python tools/summarize_profile.py gpurun_out/prof_<tag> profiles <tag> "<traffic key>".
 set -e
 PART=${1:-a}
-mkdir -p gpurun_out/profile_round4
+OUT=${OUT:-profile_out/round4}
+mkdir -p "$OUT"
 if [ "$PART" = a ]; then
-  bash tools/profile_gpu.sh r04_c3_pmsm_euler_f32 > gpurun_out/profile_round4/prof_c3.log 2>&1
-  bash tools/profile_gpu.sh r04_c2_pendulum_euler_f32 --workload pendulum_euler_f32 > gpurun_out/profile_round4/prof_c2.log 2>&1
-  bash tools/profile_gpu.sh r04_c4_msd_tsit5_f64 --workload msd_tsit5_f64 > gpurun_out/profile_round4/prof_c4.log 2>&1
-  python bench.py > gpurun_out/profile_round4/bench_default.json 2> gpurun_out/profile_round4/bench_default.err
+  bash tools/profile_gpu.sh r04_c3_pmsm_euler_f32 > $OUT/prof_c3.log 2>&1
+  bash tools/profile_gpu.sh r04_c2_pendulum_euler_f32 --workload pendulum_euler_f32 > $OUT/prof_c2.log 2>&1
+  bash tools/profile_gpu.sh r04_c4_msd_tsit5_f64 --workload msd_tsit5_f64 > $OUT/prof_c4.log 2>&1
+  python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
 elif [ "$PART" = b ]; then
-  bash tools/profile_gpu.sh r04_pmsm_tsit5_f32 --workload pmsm_tsit5_f32 > gpurun_out/profile_round4/prof_pt.log 2>&1
-  bash tools/profile_gpu.sh r04_pmsm_step --path step > gpurun_out/profile_round4/prof_step.log 2>&1
-  bash tools/profile_gpu.sh r04_em_pmsm_euler_f32 --traj-layout env_major --action-layout env_major > gpurun_out/profile_round4/prof_em.log 2>&1
+  bash tools/profile_gpu.sh r04_pmsm_tsit5_f32 --workload pmsm_tsit5_f32 > $OUT/prof_pt.log 2>&1
+  bash tools/profile_gpu.sh r04_pmsm_step --path step > $OUT/prof_step.log 2>&1
+  bash tools/profile_gpu.sh r04_em_pmsm_euler_f32 --traj-layout env_major --action-layout env_major > $OUT/prof_em.log 2>&1
   # the reference-shaped INPUT with the library's default outputs: a plain row-major actions[B, K, A] tensor read by the trajectory
   # kernel itself (round 4: 64-byte windows through LDS, no transposition pass)
-  bash tools/profile_gpu.sh r04_c3_rowmajor_actions --action-layout env_major > gpurun_out/profile_round4/prof_c3_rm.log 2>&1
+  bash tools/profile_gpu.sh r04_c3_rowmajor_actions --action-layout env_major > $OUT/prof_c3_rm.log 2>&1
 else
   for w in msd_euler_f32 tank_euler_f32 cartpole_euler_f32 acrobot_euler_f32 pmsm_euler_f64 pmsm_rk4_f32 pmsm_tsit5_f32 acrobot_tsit5_f32 pendulum_euler_f32 msd_tsit5_f64 pmsm_sat_euler_f32 pmsm_sat_tsit5_f32 pmsm_sat_euler_f64; do
-    python bench.py --workload $w --steps 20 --warmup 3 --no-cpu-baseline > gpurun_out/profile_round4/$w.json 2>> gpurun_out/profile_round4/err.txt
-    echo "$w done" >> gpurun_out/profile_round4/progress.txt
+    python bench.py --workload $w --steps 20 --warmup 3 --no-cpu-baseline > $OUT/$w.json 2>> $OUT/err.txt
+    echo "$w done" >> $OUT/progress.txt
   done
-  python bench.py --obs-only --steps 20 --warmup 3 --no-cpu-baseline > gpurun_out/profile_round4/pmsm_obsonly.json 2>> gpurun_out/profile_round4/err.txt
-  python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-pool > gpurun_out/profile_round4/pmsm_nopool.json 2>> gpurun_out/profile_round4/err.txt
+  python bench.py --obs-only --steps 20 --warmup 3 --no-cpu-baseline > $OUT/pmsm_obsonly.json 2>> $OUT/err.txt
+  python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-pool > $OUT/pmsm_nopool.json 2>> $OUT/err.txt
   for w in pendulum_euler_f32 msd_tsit5_f64 pmsm_euler_f64 pmsm_tsit5_f32; do
-    python bench.py --workload $w --steps 20 --warmup 3 --no-cpu-baseline --action-layout env_major > gpurun_out/profile_round4/${w}_rowmajor_actions.json 2>> gpurun_out/profile_round4/err.txt
+    python bench.py --workload $w --steps 20 --warmup 3 --no-cpu-baseline --action-layout env_major > $OUT/${w}_rowmajor_actions.json 2>> $OUT/err.txt
   done
-  python tools/general_path_cost.py > gpurun_out/profile_round4/general_path_cost.txt 2>&1
-  python tools/gym_cost.py > gpurun_out/profile_round4/gym_cost.txt 2>&1
-  python tools/host_overhead.py > gpurun_out/profile_round4/host_overhead.txt 2>&1
-  python tools/batch_sweep.py > gpurun_out/profile_round4/batch_sweep.txt 2>&1
+  python tools/general_path_cost.py > $OUT/general_path_cost.txt 2>&1
+  python tools/gym_cost.py > $OUT/gym_cost.txt 2>&1
+  python tools/host_overhead.py > $OUT/host_overhead.txt 2>&1
+  python tools/batch_sweep.py > $OUT/batch_sweep.txt 2>&1
 fi
