@@ -1,6 +1,7 @@
 // extern "C" entry points of libexcenv_hip.so (declared in include/excenv.h): argument validation,
 // per-thread error string, dispatch into the per-environment launch tables. No device allocation,
 // no synchronisation — only kernel enqueues on the caller's stream.
+#include <algorithm>
 #include <cstdarg>
 #include <cstdio>
 #include <dlfcn.h>
@@ -161,20 +162,28 @@ int excenv_gym_step(int env, int solver, int dtype, int64_t B, const excenv_prop
   return vt ? vt->step(sc) : rc;
 }
 
-static inline int64_t align_up(int64_t x) { return (x + 255) & ~(int64_t)255; }
-
 int64_t excenv_sim_ahead_workspace_bytes(int env, int dtype, int64_t B, int64_t K, int32_t substeps, int32_t n_control,
                                          int action_layout, int traj_layout, int with_state_traj) {
   const EnvVTable* t = table_public(env);
   if (!t || B < 0 || K < 0 || substeps < 1 || n_control < 0) return -1;
-  const int64_t w = dtype == EXCENV_F64 ? 8 : 4, N = K * substeps;
-  int64_t bytes = 0;
-  if (action_layout == EXCENV_LAYOUT_ENV_MAJOR) bytes += align_up(w * K * t->A * B);
-  if (traj_layout == EXCENV_LAYOUT_ENV_MAJOR) {
-    bytes += align_up(w * (N + 1) * (t->O + n_control) * B);
-    if (with_state_traj) bytes += (int64_t)t->S * align_up(w * (N + 1) * B);
-  }
-  return bytes;
+  return sim_workspace_bytes(t->S, t->A, t->O, dtype == EXCENV_F64 ? 8 : 4, B, K, substeps, n_control, action_layout, traj_layout,
+                             with_state_traj != 0);
+}
+
+// The facts sim_plan() decides a call's form from
+static SimFacts sim_facts(int env, const EnvVTable* t, int solver, int dtype, int64_t B, int64_t K, int32_t substeps,
+                          const excenv_props_t* props, int n_control, int semantics, int action_layout, int traj_layout,
+                          const excenv_launch_opts_t* opts) {
+  SimFacts f{};
+  f.env = env; f.S = t->S; f.A = t->A; f.O = t->O; f.elem = dtype == EXCENV_F64 ? 8 : 4; f.solver = solver; f.semantics = semantics;
+  f.B = B; f.K = K; f.substeps = substeps; f.action_layout = action_layout; f.traj_layout = traj_layout;
+  for (int j = 0; j < t->P; ++j) f.per_env_props |= props->static_params[j].per_env != nullptr;
+  for (int j = 0; j < t->S; ++j) f.per_env_props |= props->state_min[j].per_env != nullptr || props->state_max[j].per_env != nullptr;
+  for (int j = 0; j < t->A; ++j) f.per_env_props |= props->action_min[j].per_env != nullptr || props->action_max[j].per_env != nullptr;
+  f.lut = props->pmsm_lut != nullptr; f.n_control = n_control; f.refs_given = true;
+  f.al_actions = f.al_obs = f.al_state_io = f.al_straj = f.al_reward = f.al_terminated = f.al_truncated = f.al_refs = 128;
+  f.envs_per_lane = opts->envs_per_lane; f.env_major_mode = opts->env_major_mode; f.flags = opts->flags;
+  return f;
 }
 
 int excenv_sim_ahead_fuses_actions(int env, int solver, int dtype, int64_t B, int64_t K, const excenv_props_t* props,
@@ -185,10 +194,12 @@ int excenv_sim_ahead_fuses_actions(int env, int solver, int dtype, int64_t B, in
   int trc;
   const EnvVTable* t = table_for(env, props, &trc);
   if (!t) return 0;
-  (void)n_control;  // control columns are filled behind the lean kernel (control_fill_kernel): no reason not to fuse
-  return aem_applies(env, props->pmsm_lut != nullptr, props_batched(props, t->P, t->S, t->A) || with_gym != 0, t->A,
-                     dtype == EXCENV_F64 ? 8 : 4, B, K, solver, opts->envs_per_lane, action_layout, traj_layout, opts->flags, actions)
-             ? 1 : 0;
+  // what the query cannot see is assumed (include/excenv.h): references given, state and trajectory arrays 16-byte aligned
+  SimFacts f = sim_facts(env, t, solver, dtype, B, K, 1, props, n_control, EXCENV_SEM_STEP, action_layout, traj_layout, opts);
+  f.gym = with_gym != 0;
+  f.al_actions = align_of(actions);
+  f.al_obs = f.al_state_io = f.al_straj = 16;
+  return sim_plan(f).form == SIM_AEM ? 1 : 0;
 }
 
 int excenv_transpose(int dtype, int64_t M, int64_t N, const void* in, void* out, void* stream) {
@@ -220,65 +231,46 @@ int excenv_sim_ahead_ws(int env, int solver, int dtype, int64_t B, int64_t K, in
   const EnvVTable* t = table_for(env, props, &trc);
   if (!t) return trc;
   const int nc = control ? control->n_control : 0;
-  const int64_t wbytes = dtype == EXCENV_F64 ? 8 : 4;
-  // one decision for the whole call: fused env-major kernel / workspace + transposes / generic strides
-  // (the fused kernel reads the action array in whole 16-byte pieces: it must start on one and consist of whole ones —
-  // otherwise the generic-stride / workspace paths take the call)
-  const bool fused_em = B > 0 && K > 0 && aligned16(obs_traj) && aligned16(actions) && (B * K * (int64_t)t->A * wbytes) % 16 == 0 &&
-                        em_fused_eligible(opts->env_major_mode, action_layout, traj_layout, substeps, gym != nullptr, t->A, t->S,
-                                          t->O, (size_t)wbytes);
-  const int64_t need = excenv_sim_ahead_workspace_bytes(env, dtype, B, K, substeps, nc, action_layout, traj_layout,
-                                                        state_traj != nullptr);
-  // row-major actions + lane-major trajectories: the trajectory kernel reads the actions itself (no workspace, no extra pass)
-  bool refs_ok = true;  // control columns next to fused actions need every reference array (control_fill_kernel reads them)
-  for (int j = 0; j < nc; ++j) refs_ok &= control->reference[j] != nullptr;
-  const bool fused_actions =
-      aem_applies(env, props->pmsm_lut != nullptr, props_batched(props, t->P, t->S, t->A) || !refs_ok || gym != nullptr, t->A,
-                  (size_t)wbytes, B, K, solver, opts->envs_per_lane, action_layout, traj_layout, opts->flags, actions) &&
-      aligned16(obs_traj);
-  const bool via_ws = !fused_em && !fused_actions && !gym && workspace && need > 0 && workspace_bytes >= need && B > 0 &&
-                      (action_layout == EXCENV_LAYOUT_ENV_MAJOR || traj_layout == EXCENV_LAYOUT_ENV_MAJOR);
-  const int em = !fused_em ? 1 : (opts->env_major_mode == 2 ? 3 : (opts->env_major_mode == 3 ? 4 : 2));
-  if (!via_ws) {
-    SimCall sc{solver, dtype, B, K, substeps, props, control, obs_stepsize, env_tau, state_in, actions, action_layout,
-               obs_traj, state_traj, traj_layout, last_state, semantics, opts->envs_per_lane, opts->lds_pad_bytes, em, gym,
-               (hipStream_t)stream};
-    sc.flags = opts->flags;
-    return t->sim(sc);
+  SimFacts f = sim_facts(env, t, solver, dtype, B, K, substeps, props, nc, semantics, action_layout, traj_layout, opts);
+  f.gym = gym != nullptr; f.state_traj = state_traj != nullptr; f.al_actions = align_of(actions); f.al_obs = align_of(obs_traj);
+  for (int j = 0; j < t->S; ++j) {
+    f.al_state_io = std::min(f.al_state_io, std::min(align_of(state_in[j]), align_of(last_state[j])));
+    if (state_traj) f.al_straj = std::min(f.al_straj, align_of(state_traj[j]));
   }
+  if (gym) { f.al_reward = align_of(gym->reward); f.al_terminated = align_of(gym->terminated); f.al_truncated = align_of(gym->truncated); }
+  for (int j = 0; j < nc; ++j) f.al_refs = std::min(f.al_refs, align_of(control->reference[j]));  // non-NULL (check_control)
+  f.workspace = workspace != nullptr; f.al_workspace = align_of(workspace); f.workspace_bytes = workspace_bytes;
+  const SimPlan plan = sim_plan(f);
+  SimCall sc{solver, dtype, B, K, substeps, props, control, obs_stepsize, env_tau, state_in, actions, action_layout,
+             obs_traj, state_traj, traj_layout, last_state, semantics, opts->lds_pad_bytes, gym, (hipStream_t)stream, plan};
+  if (!plan.via_workspace) return t->sim(sc);
   // env-major buffers + workspace: transpose in, run the coalesced lane-major kernel, transpose out
-  const int64_t w = wbytes, N = K * substeps, OW = t->O + nc;
+  const int64_t w = f.elem, N = K * substeps, OW = t->O + nc;
   char* ws = (char*)workspace;
-  const void* k_actions = actions;
-  int k_alayout = action_layout, k_tlayout = traj_layout;
-  void* k_obs = obs_traj;
   void* k_straj[EXCENV_MAX_STATE] = {nullptr};
-  void* const* k_straj_p = state_traj;
-  hipStream_t st = (hipStream_t)stream;
+  sc.plan.via_workspace = false;  // what runs on the workspace
   if (action_layout == EXCENV_LAYOUT_ENV_MAJOR) {
-    if (int rc = launch_transpose(dtype, B, K * t->A, actions, ws, st)) { set_error("excenv_sim_ahead: action transpose failed"); return rc; }
-    k_actions = ws;
-    k_alayout = EXCENV_LAYOUT_LANE_MAJOR;
+    if (int rc = launch_transpose(dtype, B, K * t->A, actions, ws, sc.stream)) { set_error("excenv_sim_ahead: action transpose failed"); return rc; }
+    sc.actions = ws;
+    sc.action_layout = EXCENV_LAYOUT_LANE_MAJOR;
     ws += align_up(w * K * t->A * B);
   }
   if (traj_layout == EXCENV_LAYOUT_ENV_MAJOR) {
-    k_obs = ws;
+    sc.obs_traj = ws;
     ws += align_up(w * (N + 1) * OW * B);
     if (state_traj) {
       for (int j = 0; j < t->S; ++j) { k_straj[j] = ws; ws += align_up(w * (N + 1) * B); }
-      k_straj_p = k_straj;
+      sc.state_traj = k_straj;
     }
-    k_tlayout = EXCENV_LAYOUT_LANE_MAJOR;
+    sc.traj_layout = EXCENV_LAYOUT_LANE_MAJOR;
   }
-  SimCall sc{solver, dtype, B, K, substeps, props, control, obs_stepsize, env_tau, state_in, k_actions, k_alayout,
-             k_obs, k_straj_p, k_tlayout, last_state, semantics, opts->envs_per_lane, opts->lds_pad_bytes, 1, nullptr, st};
   if (int rc = t->sim(sc)) return rc;
-  g_last_launch = "transposition workspace + sim_ahead_kernel";
+  g_last_launch = plan_name(plan);
   if (traj_layout == EXCENV_LAYOUT_ENV_MAJOR) {
-    if (int rc = launch_transpose(dtype, (N + 1) * OW, B, k_obs, obs_traj, st)) { set_error("excenv_sim_ahead: obs transpose failed"); return rc; }
+    if (int rc = launch_transpose(dtype, (N + 1) * OW, B, sc.obs_traj, obs_traj, sc.stream)) { set_error("excenv_sim_ahead: obs transpose failed"); return rc; }
     if (state_traj)
       for (int j = 0; j < t->S; ++j)
-        if (int rc = launch_transpose(dtype, N + 1, B, k_straj[j], state_traj[j], st)) { set_error("excenv_sim_ahead: state transpose failed"); return rc; }
+        if (int rc = launch_transpose(dtype, N + 1, B, k_straj[j], state_traj[j], sc.stream)) { set_error("excenv_sim_ahead: state transpose failed"); return rc; }
   }
   return EXCENV_OK;
 }

@@ -3,19 +3,16 @@
 // (lane-major trajectories only). State, parameters and RK stages stay in registers for the whole trajectory.
 #pragma once
 #include "rk.hpp"
+#include "sim_plan.hpp"
 
 namespace excenv {
 
-#ifndef EXCENV_BLOCK
-#define EXCENV_BLOCK 256
-#endif
 #ifndef EXCENV_NT_STORES
 #define EXCENV_NT_STORES 1
 #endif
 #ifndef EXCENV_PINGPONG
 #define EXCENV_PINGPONG 1  // bit 0: Euler, bit 1: RK4 / Tsit5 — K loop unrolled by two with ping-pong action registers
 #endif                      // (2-step prefetch distance, 2x loop code). Measured: +3.5 % Euler, -5 % Tsit5.
-constexpr int BLOCK = EXCENV_BLOCK;
 // Deliberately broken builds for the self-test of the static guards (tools/isa_guards.py, tools/isa_guards_selftest.sh): bit 0 counts
 // one store too many in the hand-written wait of the action windows, bit 1 drops the LDS wait in front of the row barrier, bit 2
 // drops the wait state between the write of M0 and the LDS-direct load. Never set in a product build (static_assert in excenv_api.hip).
@@ -469,7 +466,7 @@ template <typename T, int V> constexpr bool aem_shape_ok() { return V * (int)siz
 #define EXCENV_AEM_NP 4  // 16-byte pieces per window (64 bytes; V * NP KiB of LDS per wave)
 #endif
 constexpr int AEM_BLOCK_BYTES = 1024 + 16;  // one LDS-direct load instruction's 1 KiB + the bank skew
-// Pieces per window. 64-byte windows everywhere (same-session sweep over nine workloads, tools/r4_aem_sweep.sh: 32-byte windows
+// Pieces per window. 64-byte windows everywhere (same-session sweep over nine workloads, profiles/r04_rowmajor_actions_pmc.md: 32-byte windows
 // cost 3 ... 30 % more: two fabric requests per 64 bytes) except acrobot, whose registers already cap it at two workgroups per
 // CU and which gains 6 % from the smaller LDS footprint.
 template <class M> constexpr int aem_np() { return M::ID == EXCENV_ACROBOT ? 2 : EXCENV_AEM_NP; }

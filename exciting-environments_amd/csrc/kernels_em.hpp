@@ -25,16 +25,10 @@
 
 namespace excenv {
 
-#ifndef EXCENV_EM_TK
-#define EXCENV_EM_TK 8  // steps per flush window for 4-byte elements (8-byte elements: half, same LDS bytes): 32-byte runs.
-                        // With aligned windows the run length no longer decides the write efficiency (every run is made of
-                        // whole 32-byte sectors), the LDS ring of TK saved states per environment decides how many waves fit
-                        // a CU: TK = 8 -> 26.5 KB per wave (PMSM), six waves per CU; TK = 16 -> 41 KB, three.
-#endif
+// TK (steps per flush window, EXCENV_EM_TK) and the LDS bytes per wave: em_tk / em_lds_elems in sim_plan.hpp.
 // Observation rows are written as non-temporal stores: complete lines that nothing reads back. The state leaves and the
 // action loads stay cacheable — non-temporal state stores measured -40 %, non-temporal action loads -30 %: the L2 merges
 // part of the state leaves' partial bursts and re-serves the action lines shared by consecutive tiles.
-constexpr int EM_LANES = 64;  // one wave per workgroup
 static_assert((EXCENV_EM_TK & (EXCENV_EM_TK - 1)) == 0 && EXCENV_EM_TK >= 2 && EXCENV_EM_TK <= EM_LANES,
               "EXCENV_EM_TK must be a power of two in [2, 64]");
 // One wave per workgroup: LDS instructions of a wave execute in issue order, so a value one lane wrote is visible to the lane
@@ -47,17 +41,9 @@ __device__ __forceinline__ void wave_sync() { asm volatile("" ::: "memory"); }
 #define EXCENV_EM_DEBUG 0  // experiments only (results are wrong): 1 skip the observation stores, 2 skip the flush, 4 skip the action-line walk
 #endif
 
-template <typename T> __host__ __device__ constexpr int em_tk() { return sizeof(T) == 4 ? EXCENV_EM_TK : EXCENV_EM_TK / 2; }
-
-// LDS elements per wave: the per-lane action line (128 bytes + one 16-byte pad), the ring of saved states, one round of
-// observation rows
-template <typename T> __host__ __device__ constexpr size_t em_lds_elems(int /*A*/, int S, int O) {
-  return (size_t)EM_LANES * (128 / sizeof(T) + 16 / sizeof(T)) + (size_t)S * EM_LANES * (em_tk<T>() + 1) + (size_t)EM_LANES * O;
-}
-
 template <class M, typename T, int SOLVER, bool AHEAD, bool BATCHED>
 __global__ void __launch_bounds__(EM_LANES) sim_ahead_em_kernel(const SimArgs<T, M> ka) {
-  constexpr int S = M::S, A = M::A, O = M::O, TK = em_tk<T>();
+  constexpr int S = M::S, A = M::A, O = M::O, TK = em_tk((int)sizeof(T));
   constexpr int VW = 16 / (int)sizeof(T);  // elements per 16-byte piece
   constexpr int EPR = EM_LANES / TK;       // environments covered by one flush round of the wave
   extern __shared__ __align__(16) unsigned char excenv_em_smem[];

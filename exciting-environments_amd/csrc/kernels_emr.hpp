@@ -30,29 +30,7 @@ namespace excenv {
 
 template <typename T, int W> struct EmrVec { typedef T type __attribute__((ext_vector_type(W))); };
 
-// Leaves that need no window: one that never changes along a trajectory — PMSM's omega_el (pmsm_env.py:509-523: the ODE has
-// no equation for it; sim_ahead keeps it constant, :785-791) — and one that is a function of other saved leaves: PMSM's torque
-// in the reference-structured trajectory, where every saved row is post-processed (pmsm_env.py:573-578, 680-688: torque from
-// the saved currents; the same device function M::torque here). On the step-semantics path row 0 carries the caller's torque
-// as it came in, so there it stays in the ring. -1: none.
-template <class M> constexpr int emr_const_leaf() { return M::IS_PMSM ? 6 : -1; }
-template <class M, bool AHEAD> constexpr int emr_derived_leaf() { return (M::IS_PMSM && AHEAD) ? 5 : -1; }
-template <class M, bool AHEAD> constexpr int emr_ring_leaves() {
-  return M::S - (emr_const_leaf<M>() >= 0 ? 1 : 0) - (emr_derived_leaf<M, AHEAD>() >= 0 ? 1 : 0);
-}
-// Steps per window. Two waves must share a SIMD (one wave alone leaves the VALU half idle: 9.9 ms for the headline launch with
-// 128-byte windows at one wave per SIMD, 7.7 ms with 64-byte windows at two), so a lane has 256 registers and the windows of
-// all ring leaves must fit next to the integration's own: 128-byte runs (whole lines, 32 registers per leaf) while the ring
-// stays within EXCENV_EMR_MAX_RING_REGS, else 64-byte runs (half lines, written 4 lanes x 16 bytes). PMSM in fp64 (5 ... 6 leaves
-// x 8 doubles next to a double-precision integration) fits since the torque leaf left the ring and the action line is loaded at
-// the crossing: two registers are spilled, reloaded only on the IEEE-division fallback path of the flush.
-#ifndef EXCENV_EMR_MAX_RING_REGS
-#define EXCENV_EMR_MAX_RING_REGS 128
-#endif
-template <class M, typename T, bool AHEAD> constexpr int emr_rows() {  // a double-precision integration needs twice the registers itself
-  return (emr_ring_leaves<M, AHEAD>() * 32 <= EXCENV_EMR_MAX_RING_REGS / ((int)sizeof(T) / 4) ? 128 : 64) / (int)sizeof(T);
-}
-template <class M, typename T> constexpr bool emr_supported() { return !M::HAS_LUT; }  // the look-up model keeps the LDS-ring kernel
+// Leaves that need no window (emr_const_leaf / emr_derived_leaf), steps per window (emr_rows): sim_plan.hpp, which picks P from them.
 // LDS bytes per wave: the transposition buffer (64 lanes x 128 bytes) and the action windows (EMR_ANP load instructions' blocks)
 constexpr int EMR_ANP = 4;  // 16-byte pieces per action window (64 bytes, fetched by 4 adjacent lanes of one LDS-direct load)
 template <class M, typename T, bool AHEAD> constexpr size_t emr_lds_bytes() { return (size_t)EM_LANES * 128 + (size_t)EMR_ANP * AEM_BLOCK_BYTES; }
@@ -81,7 +59,7 @@ template <class M, typename T, int SOLVER, bool AHEAD>
 __global__ void __launch_bounds__(EM_LANES) __attribute__((amdgpu_waves_per_eu(2))) sim_ahead_emr_kernel(const SimArgs<T, M> ka) {
   constexpr int S = M::S, A = M::A, O = M::O;
   constexpr int VW = 16 / (int)sizeof(T);   // elements per 16-byte piece
-  constexpr int W = emr_rows<M, T, AHEAD>();  // steps per window == elements per run of a state leaf
+  constexpr int W = emr_rows(M::S, M::IS_PMSM, AHEAD, (int)sizeof(T));  // steps per window == elements per run of a state leaf
   constexpr int NPC = W / VW;               // 16-byte pieces per run (4 or 8); the lanes of a wave transpose in groups of NPC
   constexpr int WL = 128 / (int)sizeof(T);  // elements per 128-byte line (action array, observation lines)
   constexpr int NPL = 8;                    // pieces per line
@@ -160,9 +138,9 @@ __global__ void __launch_bounds__(EM_LANES) __attribute__((amdgpu_waves_per_eu(2
   };
 
   if (env0 >= ka.B) return;  // no barrier is ever used: a wave without environments may leave
-  constexpr int CL = emr_const_leaf<M>();           // this leaf's saved value is st[CL] at every step
-  constexpr int DL = emr_derived_leaf<M, AHEAD>();  // this leaf's saved value is a function of other saved leaves
-  constexpr int NR = emr_ring_leaves<M, AHEAD>();
+  constexpr int CL = emr_const_leaf(M::IS_PMSM);         // this leaf's saved value is st[CL] at every step
+  constexpr int DL = emr_derived_leaf(M::IS_PMSM, AHEAD);  // this leaf's saved value is a function of other saved leaves
+  constexpr int NR = emr_ring_leaves(M::S, M::IS_PMSM, AHEAD);
   auto in_ring = [](int j) constexpr { return j != CL && j != DL; };
   // index of leaf j among the ring leaves
   auto ridx = [in_ring](int j) constexpr {

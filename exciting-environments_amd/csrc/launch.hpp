@@ -4,7 +4,6 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
-#include <cstdlib>
 #include "kernels_emr.hpp"
 #include "refgen.hpp"
 
@@ -50,60 +49,11 @@ struct SimCall {
   int traj_layout;
   void* const* last_state;
   int semantics;
-  int vec_pref;  // 0 auto, else forced envs-per-lane (1, 2, 4)
   int lds_pad;   // dynamic LDS bytes per workgroup (occupancy shaping experiments; 0 = none)
-  int em_mode;   // env-major buffers: 1 = not fused (generic strides / workspace); fused: 2 = pick the kernel, 3 = LDS-ring kernel,
-                 // 4 = register-ring kernel whenever its preconditions hold (no batch-size heuristic)
   const excenv_traj_gym_t* gym;  // optional reward / terminated / truncated trajectories
   hipStream_t stream;
-  int flags = 0;  // excenv_launch_opts_t.flags
+  SimPlan plan;  // sim_plan(): the form of the trajectory kernel
 };
-
-// Row-major actions [B][K][A] with lane-major trajectories — what a reference-shaped vmap_sim_ahead call with the library's
-// default outputs is: the widest lean instantiation reads them itself through a per-wave LDS piece ring (kernels.hpp, AEM)
-// instead of a transposition pass in front of the launch. Decided once per call (excenv_api.hip decides with the same function
-// whether a workspace transposition is needed at all). EXCENV_AEM=0 in the environment switches it off (A/B measurements).
-static inline bool aem_enabled() {
-  static const int on = [] { const char* e = std::getenv("EXCENV_AEM"); return (e && e[0] == '0') ? 0 : 1; }();
-  return on != 0;
-}
-static inline int auto_envs_per_lane(int64_t B, int vmax);
-static inline bool widest_form_pays(int64_t B, int vmax);
-static inline bool aem_applies(int env_id, bool has_lut, bool general, int A, size_t elem, int64_t B, int64_t K, int solver,
-                               int vec_pref, int action_layout, int traj_layout, int flags, const void* actions) {
-  const int vmax = 16 / (int)elem;
-  if (!aem_enabled() || (flags & EXCENV_OPT_NO_FUSED_ACTIONS) || has_lut || general) return false;
-  if (action_layout != EXCENV_LAYOUT_ENV_MAJOR || traj_layout != EXCENV_LAYOUT_LANE_MAJOR) return false;
-  if (K < 1 || (vmax % A) != 0 || (K * A) % vmax != 0) return false;  // whole 16-byte pieces per row
-  if ((B % (64 * vmax)) != 0) return false;  // whole waves: the lanes of a wave fetch action windows for each other
-  if ((reinterpret_cast<uintptr_t>(actions) & 15u) != 0) return false;
-  if ((int64_t)EXCENV_BLOCK * vmax * K * A >= ((int64_t)1 << 32)) return false;             // 32-bit element offsets inside a workgroup
-  // only where the batch takes the widest form anyway (launch_sim picks the same way)
-  int want = vec_pref > 0 ? vec_pref : (widest_form_pays(B, vmax) ? vmax : 1);
-  if (vec_pref == 0 && env_id == EXCENV_ACROBOT && solver != EXCENV_EULER && want > 2) want = 2;
-  return want == vmax;
-}
-static inline bool props_batched(const excenv_props_t* p, int P, int S, int A) {
-  bool b = false;
-  for (int j = 0; j < P; ++j) b |= p->static_params[j].per_env != nullptr;
-  for (int j = 0; j < S; ++j) b |= p->state_min[j].per_env != nullptr || p->state_max[j].per_env != nullptr;
-  for (int j = 0; j < A; ++j) b |= p->action_min[j].per_env != nullptr || p->action_max[j].per_env != nullptr;
-  return b;
-}
-
-// The fused env-major kernel applies when both layouts are env-major, substeps == 1, the caller did not opt out, no gym
-// trajectories are requested and the time tile fits LDS. Decided once per call (excenv_api.hip) and handed to launch_sim.
-// EXCENV_EM_RING=0 in the environment keeps the LDS-ring kernel (A/B measurements)
-static inline bool emr_enabled() {
-  static const int on = [] { const char* e = std::getenv("EXCENV_EM_RING"); return (e && e[0] == '0') ? 0 : 1; }();
-  return on != 0;
-}
-
-static inline bool em_fused_eligible(int em_mode, int action_layout, int traj_layout, int32_t substeps, bool with_gym,
-                                     int A, int S, int O, size_t elem) {
-  return em_mode != 1 && action_layout == EXCENV_LAYOUT_ENV_MAJOR && traj_layout == EXCENV_LAYOUT_ENV_MAJOR &&
-         substeps == 1 && !with_gym && (elem == 8 ? em_lds_elems<double>(A, S, O) : em_lds_elems<float>(A, S, O)) * elem <= 150 * 1024;
-}
 
 struct TrajGymCall {
   int dtype;
@@ -282,21 +232,6 @@ template <class M> static int pmsm_coef(const excenv_props_t* p, double env_tau,
   return EXCENV_OK;
 }
 
-// Envs per lane for a batch: the widest 16-byte form that still leaves at least one wave per SIMD on the chip
-// (256 CUs x 4 SIMDs = 1024 waves of 64 lanes); small batches run one env per lane so that the per-step dependent chain
-// of a wave is as short as possible (batch sweep).
-// Environments per lane by batch size. Two per lane from one wave per SIMD on the chip (1024 SIMDs x 64 lanes), FOUR only from two
-// waves per SIMD: at B = 2^18 four per lane leave one 256-thread workgroup per CU — round 4, same-buffers A/B and fresh processes:
-// PMSM Euler 0.411 -> 0.325 ms with two per lane, pendulum 1.259 -> 0.963, cart-pole 0.228 -> 0.153; from 2^19 on four win.
-static inline int auto_envs_per_lane(int64_t B, int vmax) {
-  int v = vmax;
-  while (v > 1 && (B / v) < (int64_t)1024 * 64 * (v >= 4 ? 2 : 1)) v >>= 1;
-  return v;
-}
-// The forms that exist only at the widest lane width (row-major actions read by the kernel, lean gym outputs) keep the earlier bound:
-// they beat what the call would fall back to (a transposition pass, the one-environment general kernel) from one wave per SIMD on.
-static inline bool widest_form_pays(int64_t B, int vmax) { return (B / vmax) >= (int64_t)1024 * 64; }
-
 template <class M, typename T> static int launch_step(const StepCall& sc) {
   StepArgs<T, M> ka;
   std::memset(&ka, 0, sizeof(ka));
@@ -365,112 +300,65 @@ template <class M, typename T> static int launch_step(const StepCall& sc) {
   return check_launch("excenv_step");
 }
 
-// Threads per workgroup of the plain lean trajectory kernel (kernels.hpp, NT): 1024 with one barrier per row for the Euler kernels of
-// the small models, BLOCK everywhere else — measured per workload (profiles/r04_pattern_sweep.md): pendulum Euler fp32 -10.6 %, fp64
-// -8 %, MSD Euler fp32 -7 %, fp64 -6 %, tank Euler fp32 -6 % (fp64 +3 %: not taken); RK4 / Tsit5 of the same models +3 ... +9 %,
-// cart-pole / acrobot Euler within 3 % either way, PMSM (256 registers) not possible.
-#ifndef EXCENV_ROW_SYNC_MIN_BATCH
-#define EXCENV_ROW_SYNC_MIN_BATCH ((int64_t)1 << 17)
-#endif
-constexpr int64_t ROW_SYNC_MIN_BATCH = EXCENV_ROW_SYNC_MIN_BATCH;
-static inline int row_sync_mode() {  // EXCENV_ROW_SYNC = 0: off, 1: barrier only, default 2: rows through LDS where possible
-  static const int mode = [] { const char* e = std::getenv("EXCENV_ROW_SYNC"); return (e && e[0] >= '0' && e[0] <= '2') ? e[0] - '0' : 2; }();
-  return mode;
-}
-static inline bool row_sync_enabled() { return row_sync_mode() != 0; }
-static inline bool wide_enabled() {  // EXCENV_WIDE=0: the 256-thread form everywhere (A/B measurements, counter passes)
-  static const int on = [] { const char* e = std::getenv("EXCENV_WIDE"); return (e && e[0] == '0') ? 0 : 1; }();
-  return on != 0;
-}
-constexpr int WIDE_THREADS = 1024;
-constexpr int64_t WIDE_MIN_WORKGROUPS = 256;  // at least one wide workgroup per CU of the MI355X, else the narrow form fills the chip better
-template <class M, typename T> constexpr bool sim_wide_ok(int solver) {
-  return solver == EXCENV_EULER && !M::HAS_LUT &&
-         (M::ID == EXCENV_PENDULUM || M::ID == EXCENV_MASS_SPRING_DAMPER || (M::ID == EXCENV_FLUID_TANK && sizeof(T) == 4));
-}
-
-// with the gym outputs' code the fp64 pendulum instantiations need 146 ... 150 registers: they would spill under the 1024-thread bound
-// (fp32: 118 ... 123 since round 5 — wide like its plain launch: 2.43 -> 2.2 ms for the gym trajectories of B = 2^22, K = 100)
-template <class M, typename T> constexpr bool sim_wide_gym_ok(int solver) {
-  return sim_wide_ok<M, T>(solver) && (M::ID != EXCENV_PENDULUM || sizeof(T) == 4);
-}
-
-template <class M, typename T, int SOLVER, bool AHEAD> static void launch_sim_v(const SimCall& sc_in, const SimArgs<T, M>& ka_in,
-                                                                                 bool general, int V, bool aem = false, bool lgym = false,
-                                                                                 int nt = BLOCK) {
-  SimArgs<T, M> ka = ka_in;
-  SimCall sc = sc_in;
-  sc.lds_pad = (int)lut_lds_bytes<T, M>(ka.kp, (size_t)sc_in.lds_pad);
-  const int64_t lanes = sc.B / V;
-  const dim3 grid((unsigned)((lanes + nt - 1) / nt)), block(nt);
-  if constexpr (sim_wide_ok<M, T>(SOLVER)) {
-    if (nt == WIDE_THREADS && !lgym) {  // the widest lean form in 1024-thread workgroups, one barrier per row (launch_sim decides)
-      constexpr int VA = 16 / (int)sizeof(T);
-      if (ka.straj[0] == nullptr) EXCENV_LAUNCH_DYN((sim_ahead_kernel<M, T, SOLVER, AHEAD, false, VA, 0, false, false, false, WIDE_THREADS>), grid, block, (size_t)sc_in.lds_pad, sc.stream, ka);
-      else EXCENV_LAUNCH_DYN((sim_ahead_kernel<M, T, SOLVER, AHEAD, false, VA, 1, false, false, false, WIDE_THREADS>), grid, block, (size_t)sc_in.lds_pad, sc.stream, ka);
-      return;
-    }
-  }
-  if constexpr (!M::HAS_LUT) {
-    if (lgym) {  // the gym trajectories out of the widest lean form (V == 16 / sizeof(T)); half of it (two environments per lane in
-      // fp32) was built and measured in round 4: PMSM 5.80 -> 7.26 ms, cart-pole 3.55 -> 4.34, acrobot 3.55 -> 4.11 — removed
-      constexpr int VA = 16 / (int)sizeof(T);
-      if constexpr (sim_wide_gym_ok<M, T>(SOLVER)) {
-        if (nt == WIDE_THREADS) {
-          if (ka.straj[0] == nullptr) EXCENV_LAUNCH_DYN((sim_ahead_kernel<M, T, SOLVER, AHEAD, false, VA, 0, false, false, true, WIDE_THREADS>), grid, block, (size_t)sc_in.lds_pad, sc.stream, ka);
-          else EXCENV_LAUNCH_DYN((sim_ahead_kernel<M, T, SOLVER, AHEAD, false, VA, 1, false, false, true, WIDE_THREADS>), grid, block, (size_t)sc_in.lds_pad, sc.stream, ka);
-          return;
-        }
-      }
-      if (ka.straj[0] == nullptr) EXCENV_LAUNCH_DYN((sim_ahead_kernel<M, T, SOLVER, AHEAD, false, VA, 0, false, false, true>), grid, block, (size_t)sc_in.lds_pad, sc.stream, ka);
-      else EXCENV_LAUNCH_DYN((sim_ahead_kernel<M, T, SOLVER, AHEAD, false, VA, 1, false, false, true>), grid, block, (size_t)sc_in.lds_pad, sc.stream, ka);
-      return;
-    }
-  }
-  if constexpr (!M::HAS_LUT && (16 / (int)sizeof(T)) % M::A == 0) {
-    if (aem) {  // row-major actions through the per-wave LDS piece ring: V == 16 / sizeof(T) (aem_applies)
-      constexpr int VA = 16 / (int)sizeof(T);
-      const size_t lds = aem_lds_bytes<M, T, VA>() + (size_t)sc_in.lds_pad;
-      if (ka.straj[0] == nullptr) EXCENV_LAUNCH_DYN((sim_ahead_kernel<M, T, SOLVER, AHEAD, false, VA, 0, false, true>), grid, block, lds, sc.stream, ka);
-      else EXCENV_LAUNCH_DYN((sim_ahead_kernel<M, T, SOLVER, AHEAD, false, VA, 1, false, true>), grid, block, lds, sc.stream, ka);
-      return;
-    }
-  }
+// The lane-major trajectory kernel in the instantiation the plan names
+template <class M, typename T, int SOLVER, bool AHEAD>
+static void launch_sim_v(const SimPlan& p, SimArgs<T, M> ka, size_t lds_pad, hipStream_t stream) {
+  const size_t lds = lut_lds_bytes<T, M>(ka.kp, lds_pad);
+  const int64_t lanes = ka.B / p.V;
+  const dim3 grid((unsigned)((lanes + p.threads - 1) / p.threads)), block(p.threads);
+  constexpr int VA = 16 / (int)sizeof(T);  // the widest form
+  // the widest forms: lean in 1024-thread workgroups (one barrier per row); lean with the gym outputs (LGYM: half of it, two
+  // environments per lane in fp32, was built and measured in round 4: PMSM 5.80 -> 7.26 ms, cart-pole 3.55 -> 4.34, acrobot 3.55 ->
+  // 4.11 — removed); row-major actions through the per-wave LDS piece ring (AEM)
+#define EXCENV_SIM_WIDEST(LDS, ...)                                                                                                     \
+  do {                                                                                                                                  \
+    if (ka.straj[0] == nullptr) EXCENV_LAUNCH_DYN((sim_ahead_kernel<M, T, SOLVER, AHEAD, false, VA, 0, __VA_ARGS__>), grid, block, LDS, stream, ka); \
+    else EXCENV_LAUNCH_DYN((sim_ahead_kernel<M, T, SOLVER, AHEAD, false, VA, 1, __VA_ARGS__>), grid, block, LDS, stream, ka);          \
+    return;                                                                                                                             \
+  } while (0)
+  constexpr int E = sizeof(T);
+  const bool wide = p.threads == WIDE_THREADS;
+  if constexpr (sim_wide_ok(M::ID, E, SOLVER, M::HAS_LUT)) if (p.form == SIM_LEAN && wide) EXCENV_SIM_WIDEST(lds, false, false, false, WIDE_THREADS);
+  if constexpr (sim_wide_gym_ok(M::ID, E, SOLVER, M::HAS_LUT)) if (p.form == SIM_LEAN_GYM && wide) EXCENV_SIM_WIDEST(lds, false, false, true, WIDE_THREADS);
+  if constexpr (!M::HAS_LUT) if (p.form == SIM_LEAN_GYM) EXCENV_SIM_WIDEST(lds, false, false, true);
+  if constexpr (!M::HAS_LUT && aem_fits(M::A, E)) if (p.form == SIM_AEM) { const size_t la = aem_lds_bytes<M, T, VA>() + lds; EXCENV_SIM_WIDEST(la, false, true); }
+#undef EXCENV_SIM_WIDEST
   // look-up models: one instantiation per place the tables live in (LDS when they fit, lut_lds_bytes above)
 #define EXCENV_SIM_LAUNCH(GEN, VV, ST)                                                                                          \
   do {                                                                                                                          \
     if constexpr (M::HAS_LUT) {                                                                                                 \
       if (ka.kp.lut_lds) {                                                                                                      \
-        EXCENV_LAUNCH_DYN((sim_ahead_kernel<M, T, SOLVER, AHEAD, GEN, VV, ST, true>), grid, block, (size_t)sc.lds_pad, sc.stream, ka); \
+        EXCENV_LAUNCH_DYN((sim_ahead_kernel<M, T, SOLVER, AHEAD, GEN, VV, ST, true>), grid, block, lds, stream, ka);            \
         return;                                                                                                                 \
       }                                                                                                                         \
     }                                                                                                                           \
-    EXCENV_LAUNCH_DYN((sim_ahead_kernel<M, T, SOLVER, AHEAD, GEN, VV, ST, false>), grid, block, (size_t)sc.lds_pad, sc.stream, ka); \
+    EXCENV_LAUNCH_DYN((sim_ahead_kernel<M, T, SOLVER, AHEAD, GEN, VV, ST, false>), grid, block, lds, stream, ka);              \
     return;                                                                                                                     \
   } while (0)
-  if (general) {
+  if (p.form == SIM_GENERAL) {
     if (ka.truncated == nullptr) EXCENV_SIM_LAUNCH(true, 1, -2);  // no gym trajectories: the instantiation without their code
     EXCENV_SIM_LAUNCH(true, 1, -1);
   }
   if (ka.straj[0] == nullptr) {  // observations only: its own instantiations (no state stores between the action loads and their waits)
     if constexpr (sizeof(T) == 4) {
-      if (V == 4) EXCENV_SIM_LAUNCH(false, 4, 0);
+      if (p.V == 4) EXCENV_SIM_LAUNCH(false, 4, 0);
     }
-    if (V == 2) EXCENV_SIM_LAUNCH(false, 2, 0);
+    if (p.V == 2) EXCENV_SIM_LAUNCH(false, 2, 0);
     EXCENV_SIM_LAUNCH(false, 1, 0);
   }
   if constexpr (sizeof(T) == 4) {
-    if (V == 4) EXCENV_SIM_LAUNCH(false, 4, 1);
+    if (p.V == 4) EXCENV_SIM_LAUNCH(false, 4, 1);
   }
-  if (V == 2) EXCENV_SIM_LAUNCH(false, 2, 1);
+  if (p.V == 2) EXCENV_SIM_LAUNCH(false, 2, 1);
   EXCENV_SIM_LAUNCH(false, 1, 1);
 #undef EXCENV_SIM_LAUNCH
 }
 
+// Validates the call, packs SimArgs and launches the form sc.plan names
 template <class M, typename T> static int launch_sim(const SimCall& sc) {
   SimArgs<T, M> ka;
   std::memset(&ka, 0, sizeof(ka));
-  const bool batched = fill_props<T, M>(ka.kp, sc.props);
+  fill_props<T, M>(ka.kp, sc.props);
   double coef;
   if (int rc = pmsm_coef<M>(sc.props, sc.env_tau, &coef, sc.semantics == EXCENV_SEM_AHEAD)) return rc;
   if (M::IS_PMSM && sc.substeps != 1) {
@@ -484,46 +372,13 @@ template <class M, typename T> static int launch_sim(const SimCall& sc) {
   const int64_t N = sc.K * sc.substeps;
   const int64_t OW = M::O + ka.n_control;
   const bool with_gym = sc.gym != nullptr;
-  // control_state columns alone (broadcast properties, no gym outputs, lane-major / tiled trajectories) do not need the
-  // one-environment-per-lane GENERAL kernel: they are constant along the trajectory and are filled by control_fill_kernel
-  // after the lean kernel has written everything else (same bytes, +1 launch, 0.52 -> 0.7 of the HBM roof at B = 2^22)
-  // the gym trajectories come out of the widest lean form too (kernels.hpp, LGYM) when everything is lane-major, the batch
-  // runs that form anyway and the flag / reward / reference arrays allow vector accesses
-  constexpr int VMAXG = 16 / (int)sizeof(T);
-  bool traj_aligned = aligned16(sc.obs_traj);  // the trajectory arrays alone (row_sync == 2 below)
-  bool vec_ok = true;  // every pointer 16-byte aligned; the general instantiation stays at one environment per lane
   for (int j = 0; j < M::S; ++j) {
     if (!sc.state_in[j] || !sc.last_state[j]) { set_error("excenv_sim_ahead: state pointer %d is NULL", j); return EXCENV_ENULL; }
     ka.state_in[j] = (const T*)sc.state_in[j];
     ka.last_state[j] = (T*)sc.last_state[j];
     ka.straj[j] = sc.state_traj ? (T*)sc.state_traj[j] : nullptr;
     if (sc.state_traj && !sc.state_traj[j]) { set_error("excenv_sim_ahead: state_traj pointer %d is NULL", j); return EXCENV_ENULL; }
-    vec_ok &= aligned16(ka.state_in[j]) && aligned16(ka.last_state[j]) && aligned16(ka.straj[j]);
-    traj_aligned &= aligned16(ka.straj[j]);
   }
-  // Everything that keeps a call from the widest lane form keeps it from the lean gym form too, and the call then takes the general
-  // instantiation like any other gym call (round 4 returned an "internal error" for two such cases: acrobot RK4 / Tsit5 with default
-  // options — the lane-width cap below — and state / trajectory / action arrays that are not 16-byte aligned).
-  bool lean_gym = with_gym && !batched && !M::HAS_LUT && ka.n_control <= M::S && sc.action_layout == EXCENV_LAYOUT_LANE_MAJOR &&
-                  sc.traj_layout == EXCENV_LAYOUT_LANE_MAJOR && sc.B > 0 && (sc.B % VMAXG) == 0 &&
-                  (sc.vec_pref > 0 ? sc.vec_pref == VMAXG : widest_form_pays(sc.B, VMAXG)) &&
-                  vec_ok && aligned16(sc.actions) && aligned16(sc.obs_traj) &&
-                  !(sc.vec_pref == 0 && M::ID == EXCENV_ACROBOT && sc.solver != EXCENV_EULER) &&
-                  aligned16(sc.gym->reward) && ((uintptr_t)sc.gym->terminated % VMAXG) == 0 && ((uintptr_t)sc.gym->truncated % VMAXG) == 0;
-  for (int j = 0; lean_gym && j < ka.n_control; ++j) lean_gym = sc.control->reference[j] != nullptr && aligned16(sc.control->reference[j]);
-  // the four-leaf models in fp64 with an RK solver would need more than 256 registers in that form (one wave per SIMD): general
-  if (sizeof(T) == 8 && M::S == 4 && sc.solver != EXCENV_EULER) lean_gym = false;
-  // row-major actions the lean kernel can read itself (AEM) are no reason for the general kernel either: the control columns are
-  // filled behind it all the same (round 5; before, a control_state alone sent a plain [B, K, A] call to the transposition pass)
-  const bool aem_candidate = !batched && !with_gym && vec_ok && aligned16(sc.obs_traj) &&
-                             aem_applies(M::ID, M::HAS_LUT, false, M::A, sizeof(T), sc.B, sc.K, sc.solver, sc.vec_pref, sc.action_layout,
-                                         sc.traj_layout, sc.flags, sc.actions);
-  bool split_control = !batched && (!with_gym || lean_gym) && ka.n_control > 0 && sc.traj_layout != EXCENV_LAYOUT_ENV_MAJOR &&
-                       (sc.action_layout != EXCENV_LAYOUT_ENV_MAJOR || aem_candidate) && sc.B > 0;
-  if (split_control) {
-    for (int j = 0; j < ka.n_control; ++j) split_control &= sc.control->reference[j] != nullptr;
-  }
-  bool general = batched || (ka.n_control > 0 && !split_control) || (with_gym && !lean_gym);
   ka.actions = (const T*)sc.actions;
   ka.obs = (T*)sc.obs_traj;
   constexpr int64_t TILE = EXCENV_TILE;  // envs per tile of the tiled layout (== one workgroup at V = TILE/BLOCK)
@@ -581,30 +436,14 @@ template <class M, typename T> static int launch_sim(const SimCall& sc) {
     }
   }
 
-  if (sc.em_mode >= 2 && !em_fused_eligible(0, sc.action_layout, sc.traj_layout, sc.substeps, sc.gym != nullptr, M::A, M::S, M::O,
-                                            sizeof(T))) {  // em_mode >= 2 is produced by excenv_sim_ahead_ws only; never trust it blindly
-    set_error("excenv_sim_ahead: internal error: fused env-major kernel selected for an ineligible call");
-    return EXCENV_EINVAL;
-  }
-  if constexpr (emr_supported<M, T>()) {
-  if ((sc.em_mode == 2 || sc.em_mode == 4) && !general && emr_enabled()) {
-    // register-ring form (kernels_emr.hpp): whole-line stores. Needs 128-byte aligned trajectory arrays and enough environments
-    // to fill waves whose lanes are P environments apart.
-    const bool ahead = sc.semantics == EXCENV_SEM_AHEAD;
-    const int64_t W = ahead ? emr_rows<M, T, true>() : emr_rows<M, T, false>();  // steps per window
-    auto period = [](int64_t x, int64_t m) { int64_t g = m, y = x % m; while (y) { const int64_t t = g % y; g = y; y = t; } return m / g; };
-    const int64_t P = period(sc.K + 1, W);
-    // action rows must consist of whole 16-byte pieces (they are fetched as 64-byte windows by LDS-direct loads)
-    bool ok = ((uintptr_t)ka.obs % 128) == 0 && (sc.em_mode == 4 || sc.B >= 16 * EM_LANES * P) &&
-              (sc.K * M::A * (int64_t)sizeof(T)) % 16 == 0 && aligned16(ka.actions) &&
-              EM_LANES * P * (sc.K + 1) * M::O * (int64_t)sizeof(T) < ((int64_t)1 << 31);  // 32-bit lane offsets
-    for (int j = 0; j < M::S; ++j) ok &= ka.straj[j] == nullptr || ((uintptr_t)ka.straj[j] % 128) == 0;
-    if (ok) {
+  const SimPlan& p = sc.plan;
+  if constexpr (emr_supported(M::HAS_LUT)) {
+    if (p.form == SIM_EMR) {  // register-ring form (kernels_emr.hpp): whole-line stores, lanes p.period environments apart
       SimArgs<T, M> kr = ka;
-      kr.a_wg = P;
-      const size_t emr_lds = ahead ? emr_lds_bytes<M, T, true>() : emr_lds_bytes<M, T, false>();
-      const int64_t per = EM_LANES * P;
-      const dim3 grid((unsigned)(((sc.B + per - 1) / per) * P)), block(EM_LANES);
+      kr.a_wg = p.period;
+      const size_t emr_lds = sc.semantics == EXCENV_SEM_AHEAD ? emr_lds_bytes<M, T, true>() : emr_lds_bytes<M, T, false>();
+      const int64_t per = EM_LANES * p.period;
+      const dim3 grid((unsigned)(((sc.B + per - 1) / per) * p.period)), block(EM_LANES);
 #define EXCENV_EMR_CASE(SOLV)                                                                                                 \
   case SOLV:                                                                                                                  \
     if (sc.semantics == EXCENV_SEM_AHEAD) EXCENV_LAUNCH_DYN((sim_ahead_emr_kernel<M, T, SOLV, true>), grid, block, emr_lds, sc.stream, kr); \
@@ -617,25 +456,20 @@ template <class M, typename T> static int launch_sim(const SimCall& sc) {
         default: set_error("bad solver id %d", sc.solver); return EXCENV_EINVAL;
       }
 #undef EXCENV_EMR_CASE
-      g_last_launch = "sim_ahead_emr_kernel";
+      g_last_launch = plan_name(p);
       return check_launch("excenv_sim_ahead (env-major fused, register ring)");
     }
   }
-  }
-  if (sc.em_mode >= 2) {  // decided by the caller (em_fused_eligible): fused env-major kernel, one wave per 64 envs,
-                          // TK steps staged in LDS, per-env contiguous runs written out
-    const size_t lds = em_lds_elems<T>(M::A, M::S, M::O) * sizeof(T);
+  if (p.form == SIM_EM || p.form == SIM_EM_GENERAL) {  // fused env-major kernel, one wave per 64 envs, TK steps staged in LDS,
+                                                       // per-env contiguous runs written out
+    const size_t lds = em_lds_elems((int)sizeof(T), M::S, M::O) * sizeof(T);
     const dim3 grid((unsigned)((sc.B + EM_LANES - 1) / EM_LANES)), block(EM_LANES);
-#define EXCENV_EM_CASE(SOLV)                                                                                             \
-  case SOLV:                                                                                                             \
-    if (sc.semantics == EXCENV_SEM_AHEAD) {                                                                              \
-      if (general) EXCENV_LAUNCH_DYN((sim_ahead_em_kernel<M, T, SOLV, true, true>), grid, block, lds, sc.stream, ka);   \
-      else EXCENV_LAUNCH_DYN((sim_ahead_em_kernel<M, T, SOLV, true, false>), grid, block, lds, sc.stream, ka);          \
-    } else {                                                                                                             \
-      if (general) EXCENV_LAUNCH_DYN((sim_ahead_em_kernel<M, T, SOLV, false, true>), grid, block, lds, sc.stream, ka);  \
-      else EXCENV_LAUNCH_DYN((sim_ahead_em_kernel<M, T, SOLV, false, false>), grid, block, lds, sc.stream, ka);         \
-    }                                                                                                                    \
-    break;
+#define EXCENV_EM_LAUNCH(SOLV, AH)                                                                                       \
+  if (general) EXCENV_LAUNCH_DYN((sim_ahead_em_kernel<M, T, SOLV, AH, true>), grid, block, lds, sc.stream, ka);         \
+  else EXCENV_LAUNCH_DYN((sim_ahead_em_kernel<M, T, SOLV, AH, false>), grid, block, lds, sc.stream, ka)
+#define EXCENV_EM_CASE(SOLV) \
+  case SOLV: if (sc.semantics == EXCENV_SEM_AHEAD) { EXCENV_EM_LAUNCH(SOLV, true); } else { EXCENV_EM_LAUNCH(SOLV, false); } break;
+    const bool general = p.form == SIM_EM_GENERAL;
     switch (sc.solver) {
       EXCENV_EM_CASE(EXCENV_EULER)
       EXCENV_EM_CASE(EXCENV_RK4)
@@ -643,78 +477,13 @@ template <class M, typename T> static int launch_sim(const SimCall& sc) {
       default: set_error("bad solver id %d", sc.solver); return EXCENV_EINVAL;
     }
 #undef EXCENV_EM_CASE
-    g_last_launch = general ? "sim_ahead_em_kernel (general)" : "sim_ahead_em_kernel";
+#undef EXCENV_EM_LAUNCH
+    g_last_launch = plan_name(p);
     return check_launch("excenv_sim_ahead (env-major fused)");
   }
-  const bool aem = vec_ok && aligned16(ka.obs) &&
-                   aem_applies(M::ID, M::HAS_LUT, general, M::A, sizeof(T), sc.B, sc.K, sc.solver, sc.vec_pref, sc.action_layout,
-                               sc.traj_layout, sc.flags, ka.actions);
-  vec_ok &= (sc.action_layout != EXCENV_LAYOUT_ENV_MAJOR || aem) && (sc.traj_layout != EXCENV_LAYOUT_ENV_MAJOR);
-  vec_ok &= aligned16(ka.actions) && aligned16(ka.obs);
-  constexpr int VMAX = 16 / (int)sizeof(T);
-  int V = 1;
-  if (general) vec_ok = false;  // one environment per lane (two, each with its own property set, measured no faster: DESIGN.md §4.1)
-  if (vec_ok) {
-    int want = sc.vec_pref > 0 ? sc.vec_pref : ((aem || lean_gym) ? VMAX : auto_envs_per_lane(sc.B, VMAX));
-    // acrobot RK4 / Tsit5 is VALU-bound with the largest register footprint of all instantiations: two envs per lane keep
-    // a third wave per SIMD resident (measured +7 % over four)
-    if (sc.vec_pref == 0 && M::ID == EXCENV_ACROBOT && sc.solver != EXCENV_EULER && want > 2) want = 2;
-    // look-up models: the interpolation code per environment is large (instruction cache) and keeps six table values per
-    // environment live across the step (V = 4 needs > 256 registers): measured best at two environments per lane for Euler
-    // and one for RK4 / Tsit5
-    if (sc.vec_pref == 0 && M::HAS_LUT) {
-      const int cap = (sc.solver == EXCENV_EULER) ? 2 : 1;
-      if (want > cap) want = cap;
-    }
-    // PMSM observations only in fp32: the arithmetic of a step is the full launch's, the bytes are 40 of 68 — VALU floor and memory
-    // floor meet (2.7 / 2.8 ms) and what counts is how well they overlap: two environments per lane (116 registers, four waves
-    // per SIMD) instead of four (186, two waves). Same-buffers A/B: Euler 3.555 -> 3.157 ms (0.59 -> 0.66 of the roof), RK4 4.457 ->
-    // 4.010, Tsit5 5.435 -> 4.784; with full outputs four stay faster (RK4 5.64 vs 6.19, Tsit5 6.25 vs 6.37).
-    // Round 5, after the instruction diet (same-buffers A/B, one / two / four per lane): Euler 3.34 / 3.49 / 3.46 ms — one; RK4 3.79 /
-    // 3.72 / 4.04 and Tsit5 4.32 / 4.19 / 4.73 — two.
-    if (sc.vec_pref == 0 && M::IS_PMSM && !M::HAS_LUT && sizeof(T) == 4 && ka.straj[0] == nullptr && !aem && !lean_gym) {
-      const int cap = (sc.solver == EXCENV_EULER) ? 1 : 2;
-      if (want > cap) want = cap;
-    }
-    // cart-pole RK4 / Tsit5 and pendulum Tsit5 in fp32: the same trade (registers for a resident wave) — same-buffers A/B with two
-    // instead of four environments per lane: cart-pole RK4 4.646 -> 4.323 ms, Tsit5 7.046 -> 6.091, pendulum Tsit5 2.637 -> 2.477
-    // (pendulum RK4, mass-spring-damper, tank: four stay faster or equal)
-    if (sc.vec_pref == 0 && sizeof(T) == 4 && !aem && !lean_gym && want > 2 &&
-        ((M::ID == EXCENV_CART_POLE && sc.solver != EXCENV_EULER) || (M::ID == EXCENV_PENDULUM && sc.solver == EXCENV_TSIT5)))
-      want = 2;
-    if (want > VMAX) want = VMAX;
-    while (want > 1 && (sc.B % want) != 0) want >>= 1;
-    V = want;
-  }
-  if (lean_gym && (general || V != VMAX)) { set_error("excenv_sim_ahead: internal error: lean gym outputs need %d environments per lane", VMAX); return EXCENV_EINVAL; }
-  if (aem && V != VMAX) { set_error("excenv_sim_ahead: internal error: fused row-major actions need %d environments per lane", VMAX); return EXCENV_EINVAL; }
-  if (tiled_a || tiled_t) {  // a workgroup must not straddle tiles
-    constexpr int VT = (int)(TILE / BLOCK);
-    if (VT > VMAX || general || !vec_ok) {
-      if (TILE % BLOCK != 0) { set_error("tiled layout: TILE %% BLOCK != 0"); return EXCENV_EINVAL; }
-      V = 1;
-    } else {
-      V = VT;
-    }
-  }
-  // one environment per lane at a batch that fills the chip several times over: the four waves of a workgroup store each row
-  // together (kernels.hpp row_sync). EXCENV_ROW_SYNC=0 switches it off (A/B measurements).
-  // (not with the gym outputs' code in the loop: with that much arithmetic per row lockstep costs more than the stores gain —
-  // PMSM 7.06 -> 8.59 ms, pendulum 4.64 -> 5.28, acrobot 7.0 -> 8.0 measured)
-  ka.row_sync = (V == 1 && !with_gym && sc.traj_layout == EXCENV_LAYOUT_LANE_MAJOR && sc.B >= ROW_SYNC_MIN_BATCH && row_sync_enabled()) ? 1 : 0;
-  size_t row_lds = 0;
-  if (ka.row_sync && !M::HAS_LUT && !aem && (sc.B % BLOCK) == 0 && traj_aligned && row_sync_mode() >= 2) {
-    // whole workgroups and aligned arrays: the rows leave through LDS as 16-byte stores (kernels.hpp, row_sync == 2)
-    const size_t ns = (size_t)OW + (ka.straj[0] ? M::S : 0);
-    const size_t bytes = 2 * ns * BLOCK * sizeof(T);
-    if (bytes <= ((size_t)64 << 10)) { ka.row_sync = 2; row_lds = bytes; }
-  }
-  int nt = BLOCK;
-  if (wide_enabled() && sim_wide_ok<M, T>(sc.solver) && (!lean_gym || sim_wide_gym_ok<M, T>(sc.solver)) && !general && !aem && !tiled_a && !tiled_t && V == VMAX &&
-      sc.B / V >= WIDE_THREADS * WIDE_MIN_WORKGROUPS)
-    nt = WIDE_THREADS;
+  ka.row_sync = p.row_sync;
   {  // element offset of workgroup w's first env in each stream
-    const int64_t wg_envs = (int64_t)nt * V;
+    const int64_t wg_envs = (int64_t)p.threads * p.V;
     auto wg_off = [&](int layout, int64_t sb, int64_t per_tile) -> int64_t {
       if (layout == EXCENV_LAYOUT_TILED) return (wg_envs == TILE) ? per_tile : -1;
       return wg_envs * sb;
@@ -727,12 +496,11 @@ template <class M, typename T> static int launch_sim(const SimCall& sc) {
       return EXCENV_EUNSUPPORTED;
     }
   }
-  SimCall scl = sc;
-  scl.lds_pad += (int)row_lds;
-#define EXCENV_SIM_CASE(SOLV)                                                         \
-  case SOLV:                                                                          \
-    if (sc.semantics == EXCENV_SEM_AHEAD) launch_sim_v<M, T, SOLV, true>(scl, ka, general, V, aem && V == VMAX, lean_gym, nt);  \
-    else launch_sim_v<M, T, SOLV, false>(scl, ka, general, V, aem && V == VMAX, lean_gym, nt);                         \
+  const size_t lds_pad = (size_t)sc.lds_pad + p.row_lds;
+#define EXCENV_SIM_CASE(SOLV)                                                                \
+  case SOLV:                                                                                 \
+    if (sc.semantics == EXCENV_SEM_AHEAD) launch_sim_v<M, T, SOLV, true>(p, ka, lds_pad, sc.stream); \
+    else launch_sim_v<M, T, SOLV, false>(p, ka, lds_pad, sc.stream);                         \
     break;
   switch (sc.solver) {
     EXCENV_SIM_CASE(EXCENV_EULER)
@@ -741,9 +509,9 @@ template <class M, typename T> static int launch_sim(const SimCall& sc) {
     default: set_error("bad solver id %d", sc.solver); return EXCENV_EINVAL;
   }
 #undef EXCENV_SIM_CASE
-  g_last_launch = general ? "sim_ahead_kernel (general)" : (lean_gym ? (nt > BLOCK ? "sim_ahead_kernel (lean, gym outputs, 1024 threads)" : "sim_ahead_kernel (lean, gym outputs)") : aem ? "sim_ahead_kernel (row-major actions fused)" : (V == 1 ? "sim_ahead_kernel (V=1)" : (V == 2 ? (nt > BLOCK ? "sim_ahead_kernel (V=2, 1024 threads)" : "sim_ahead_kernel (V=2)") : (nt > BLOCK ? "sim_ahead_kernel (V=4, 1024 threads)" : "sim_ahead_kernel (V=4)"))));
+  g_last_launch = plan_name(p);
   if (int rc = check_launch("excenv_sim_ahead")) return rc;
-  if (split_control && !general) {
+  if (p.split_control) {
     ControlFillArgs<T, M> fa;
     std::memset(&fa, 0, sizeof(fa));
     fa.kp = ka.kp;

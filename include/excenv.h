@@ -241,10 +241,10 @@ int excenv_sim_ahead_ws(int env, int solver, int dtype, int64_t B, int64_t K, in
  * vmap_sim_ahead is handed, core_env.py:571-616) inside the lane-major trajectory kernel itself — 64-byte windows of every
  * environment's row through LDS, no transposition pass, no workspace — else 0 (then a workspace of
  * excenv_sim_ahead_workspace_bytes lets the library transpose them first). Applies to broadcast properties without gym
- * trajectories (control columns are fine when every control->reference[j] is given: they are filled by a second small launch
- * behind the lean kernel; n_control is ignored by this query), the batch sizes that run V = 16 / sizeof(dtype) environments per lane with B % (64 V) == 0,
- * K * A * sizeof(dtype) a multiple of 16 and 16-byte aligned actions; the state / output pointers must be 16-byte aligned as
- * for every vectorised launch. */
+ * trajectories (control columns are filled by a second small launch behind the lean kernel), the batch sizes that run
+ * V = 16 / sizeof(dtype) environments per lane with B % (64 V) == 0, K * A * sizeof(dtype) a multiple of 16 and 16-byte aligned
+ * actions. The answer assumes what the query cannot see: every control->reference[j] non-NULL, and the state_in, last_state,
+ * state_traj and obs_traj arrays 16-byte aligned (as for every vectorised launch). */
 int excenv_sim_ahead_fuses_actions(int env, int solver, int dtype, int64_t B, int64_t K, const excenv_props_t* props,
                                    int32_t n_control, int with_gym, int action_layout, int traj_layout, const void* actions,
                                    const excenv_launch_opts_t* opts);

@@ -568,3 +568,39 @@ def test_gym_trajectories_with_a_misaligned_array_take_the_general_kernel(which)
     a, b = results
     assert torch.equal(a["obs"], b["obs"]) and torch.equal(a["rew"], b["rew"]) and torch.equal(a["term"], b["term"])
     assert torch.equal(a["trunc"], b["trunc"]) and all(torch.equal(x, y) for x, y in zip(a["straj"], b["straj"]))
+
+
+def test_gym_trajectories_with_truncated_off_a_dword_take_the_general_kernel():
+    """pendulum fp64 without control columns stores the V * TW = 2 * 2 truncated bytes of a lane as ONE 4-byte
+    store (kernels.hpp store_flag_bytes), so `truncated` 2 bytes off a 4-byte boundary cannot take the lean gym form: the call runs
+    the general kernel and gives the aligned call's bits."""
+    from exciting_environments_amd import _native
+
+    B, K = 1 << 17, 5
+    dt = torch.float64
+    env, props_o, keep, spec = make_env("pendulum", B, dt, solver="euler")
+    dev = env.device
+    props, pkeep = env._props_for(env.env_properties, B)
+    g = torch.Generator(device="cpu").manual_seed(7)
+    st_in = [(torch.rand(B, generator=g, dtype=dt) * 8 - 4).to(dev), (torch.rand(B, generator=g, dtype=dt) * 30 - 15).to(dev)]  # |omega| > 10: flags set
+    acts = (torch.rand((K, 1, B), generator=g, dtype=dt) * 2 - 1).to(dev)
+    results = []
+    for off in (0, 2):
+        obs = torch.zeros(((K + 1) * 2 * B,), dtype=dt, device=dev)
+        straj = [torch.zeros(((K + 1) * B,), dtype=dt, device=dev) for _ in range(2)]
+        last = [torch.zeros(B, dtype=dt, device=dev) for _ in range(2)]
+        rew = torch.zeros((K, B), dtype=dt, device=dev)
+        term = torch.zeros((K, B), dtype=torch.bool, device=dev)
+        n = (K + 1) * B * 2  # excenv_truncated_width(pendulum, 0) = 2 flags per environment
+        trunc = torch.zeros(n + 16, dtype=torch.bool, device=dev)[off:off + n].view(K + 1, B, 2)
+        assert trunc.data_ptr() % 4 == off
+        _native.sim_ahead(env.ENV_ID, env._solver.id, dt, B, K, 1, props, None, env.tau, env.tau, st_in, acts,
+                          _native.LAYOUT_LANE_MAJOR, obs, straj, _native.LAYOUT_LANE_MAJOR, last, _native.SEM_AHEAD, None,
+                          _native.launch_opts(envs_per_lane=2), (rew, term, trunc))
+        torch.cuda.synchronize()
+        assert _native.last_launch() == ("sim_ahead_kernel (general)" if off else "sim_ahead_kernel (lean, gym outputs)")
+        results.append(dict(obs=obs, straj=straj, last=last, rew=rew, term=term, trunc=trunc.clone()))
+    a, b = results
+    assert torch.equal(a["obs"], b["obs"]) and torch.equal(a["rew"], b["rew"]) and torch.equal(a["term"], b["term"])
+    assert torch.equal(a["trunc"], b["trunc"]) and a["trunc"].any()
+    assert all(torch.equal(x, y) for x, y in zip(a["straj"] + a["last"], b["straj"] + b["last"]))

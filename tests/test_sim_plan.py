@@ -1,0 +1,190 @@
+"""The trajectory kernel's form for a call (csrc/sim_plan.hpp), checked without a GPU: the planner header is compiled with the host
+C++ compiler next to a small driver that reads call facts and prints the plan. The table covers every form, each lane-width cap,
+row_sync 0 / 1 / 2, the workgroup widths, the tiled layout, the workspace path, the flag alignment of the lean gym form and the
+shapes behind the last_launch() assertions of the GPU suite."""
+import os
+import shutil
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "exciting-environments_amd", "csrc")
+CXX = shutil.which(os.environ.get("CXX", "c++")) or shutil.which("g++") or shutil.which("clang++")
+
+FIELDS = ("env S A O elem solver semantics B K substeps action_layout traj_layout per_env_props lut n_control refs_given gym "
+          "state_traj al_actions al_obs al_state_io al_straj al_reward al_terminated al_truncated al_refs envs_per_lane "
+          "env_major_mode flags workspace al_workspace workspace_bytes").split()
+DRIVER = r"""
+#include <cstdio>
+#include "sim_plan.hpp"
+int main() {
+  long long v[%d];
+  while (true) {
+    for (int i = 0; i < %d; ++i) if (std::scanf("%%lld", &v[i]) != 1) return 0;
+    excenv::SimFacts f{};
+    int i = 0;
+%s
+    const excenv::SimPlan p = excenv::sim_plan(f);
+    std::printf("%%d %%d %%d %%d %%d %%d %%d %%lld|%%s\n", (int)p.form, (int)p.via_workspace, p.V, p.threads, p.row_sync, p.row_lds,
+                (int)p.split_control, (long long)p.period, excenv::plan_name(p));
+  }
+}
+""" % (len(FIELDS), len(FIELDS), "\n".join(f"    f.{n} = (decltype(f.{n}))v[i++];" for n in FIELDS))
+
+GENERAL, LEAN, LEAN_GYM, AEM, EM, EM_GENERAL, EMR = range(7)
+MODELS = {"pendulum": (0, 2, 1, 2), "mass_spring_damper": (1, 2, 1, 2), "cartpole": (2, 4, 1, 4), "acrobot": (3, 4, 1, 4),
+          "fluid_tank": (4, 1, 1, 1), "pmsm": (5, 7, 2, 8)}
+SOLVERS = {"euler": 0, "rk4": 1, "tsit5": 2}
+EM_L, LANE, TILED = 0, 1, 2
+
+
+def facts(model="pendulum", dtype=4, solver="euler", B=1 << 20, K=100, **kw):
+    env, S, A, O = MODELS[model]
+    f = dict(env=env, S=S, A=A, O=O, elem=dtype, solver=SOLVERS[solver], semantics=0, B=B, K=K, substeps=1, action_layout=LANE,
+             traj_layout=LANE, per_env_props=0, lut=0, n_control=0, refs_given=1, gym=0, state_traj=1, al_actions=128, al_obs=128,
+             al_state_io=128, al_straj=128, al_reward=128, al_terminated=128, al_truncated=128, al_refs=128, envs_per_lane=0,
+             env_major_mode=0, flags=0, workspace=0, al_workspace=128, workspace_bytes=0)
+    for k, v in kw.items():
+        assert k in f, k
+        f[k] = int(v)
+    return f
+
+
+F32, F64 = 4, 8
+M17, M18, M20, M22 = 1 << 17, 1 << 18, 1 << 20, 1 << 22
+# (id, facts, expected: form, V, threads, row_sync, split_control, period (EMR) / None, last_launch name)
+CASES = [
+    # every form
+    ("general/per-env properties", facts(per_env_props=1, state_traj=0), (GENERAL, 1, 256, 2, 0, 0, "sim_ahead_kernel (general)")),
+    ("lean V=1", facts(B=1 << 16), (LEAN, 1, 256, 0, 0, 0, "sim_ahead_kernel (V=1)")),
+    ("lean V=2", facts(B=M18), (LEAN, 2, 256, 0, 0, 0, "sim_ahead_kernel (V=2)")),
+    ("lean V=4 1024 threads", facts(), (LEAN, 4, 1024, 0, 0, 0, "sim_ahead_kernel (V=4, 1024 threads)")),
+    ("lean V=4", facts("pmsm", B=M22), (LEAN, 4, 256, 0, 0, 0, "sim_ahead_kernel (V=4)")),
+    ("lean V=2 1024 threads fp64", facts(dtype=F64), (LEAN, 2, 1024, 0, 0, 0, "sim_ahead_kernel (V=2, 1024 threads)")),
+    ("lean gym", facts("pmsm", gym=1), (LEAN_GYM, 4, 256, 0, 0, 0, "sim_ahead_kernel (lean, gym outputs)")),
+    ("lean gym 1024 threads", facts(gym=1), (LEAN_GYM, 4, 1024, 0, 0, 0, "sim_ahead_kernel (lean, gym outputs, 1024 threads)")),
+    ("row-major actions", facts(action_layout=EM_L), (AEM, 4, 256, 0, 0, 0, "sim_ahead_kernel (row-major actions fused)")),
+    ("row-major actions, control columns", facts(action_layout=EM_L, n_control=1),
+     (AEM, 4, 256, 0, 1, 0, "sim_ahead_kernel (row-major actions fused)")),
+    ("row-major actions opted out", facts(action_layout=EM_L, flags=1), (LEAN, 1, 256, 2, 0, 0, "sim_ahead_kernel (V=1)")),
+    ("row-major actions opted out, workspace", facts(action_layout=EM_L, flags=1, workspace=1, workspace_bytes=1 << 40),
+     (LEAN, 4, 1024, 0, 0, 0, "transposition workspace + sim_ahead_kernel")),
+    ("env-major LDS ring", facts("pmsm", B=4096, K=64, action_layout=EM_L, traj_layout=EM_L), (EM, 1, 64, 0, 0, 0, "sim_ahead_em_kernel")),
+    ("env-major LDS ring, general", facts("pmsm", B=65536, K=64, action_layout=EM_L, traj_layout=EM_L, per_env_props=1),
+     (EM_GENERAL, 1, 64, 0, 0, 0, "sim_ahead_em_kernel (general)")),
+    ("env-major LDS ring forced", facts("pmsm", B=65536, K=64, action_layout=EM_L, traj_layout=EM_L, env_major_mode=2),
+     (EM, 1, 64, 0, 0, 0, "sim_ahead_em_kernel")),
+    ("register ring", facts("pmsm", B=65536, K=64, action_layout=EM_L, traj_layout=EM_L), (EMR, 1, 64, 0, 0, 16, "sim_ahead_emr_kernel")),
+    ("register ring needs 128-byte trajectories", facts("pmsm", B=65536, K=64, action_layout=EM_L, traj_layout=EM_L, al_obs=64),
+     (EM, 1, 64, 0, 0, 0, "sim_ahead_em_kernel")),
+    ("env-major never fused", facts("pmsm", B=65536, K=64, action_layout=EM_L, traj_layout=EM_L, env_major_mode=1),
+     (LEAN, 1, 256, 0, 0, 0, "sim_ahead_kernel (V=1)")),
+    ("workspace", facts(action_layout=EM_L, traj_layout=EM_L, env_major_mode=1, workspace=1, workspace_bytes=1 << 40),
+     (LEAN, 4, 1024, 0, 0, 0, "transposition workspace + sim_ahead_kernel")),
+    ("workspace too small", facts(action_layout=EM_L, traj_layout=EM_L, env_major_mode=1, workspace=1, workspace_bytes=4096),
+     (LEAN, 1, 256, 0, 0, 0, "sim_ahead_kernel (V=1)")),
+    ("tiled", facts("pmsm", action_layout=TILED, traj_layout=TILED), (LEAN, 4, 256, 0, 0, 0, "sim_ahead_kernel (V=4)")),
+    ("tiled fp64", facts("pmsm", dtype=F64, action_layout=TILED, traj_layout=TILED), (LEAN, 1, 256, 0, 0, 0, "sim_ahead_kernel (V=1)")),
+    ("tiled with control columns", facts("pmsm", traj_layout=TILED, n_control=2), (LEAN, 4, 256, 0, 1, 0, "sim_ahead_kernel (V=4)")),
+    # lane-width caps (default options)
+    ("acrobot RK4", facts("acrobot", solver="rk4", B=M22), (LEAN, 2, 256, 0, 0, 0, "sim_ahead_kernel (V=2)")),
+    ("LUT Euler", facts("pmsm", B=M22, lut=1), (LEAN, 2, 256, 0, 0, 0, "sim_ahead_kernel (V=2)")),
+    ("LUT RK4", facts("pmsm", solver="rk4", B=M22, lut=1), (LEAN, 1, 256, 1, 0, 0, "sim_ahead_kernel (V=1)")),
+    ("PMSM fp32 observations only Euler", facts("pmsm", B=M22, state_traj=0), (LEAN, 1, 256, 2, 0, 0, "sim_ahead_kernel (V=1)")),
+    ("PMSM fp32 observations only RK4", facts("pmsm", solver="rk4", B=M22, state_traj=0), (LEAN, 2, 256, 0, 0, 0, "sim_ahead_kernel (V=2)")),
+    ("cart-pole RK4", facts("cartpole", solver="rk4", B=M22), (LEAN, 2, 256, 0, 0, 0, "sim_ahead_kernel (V=2)")),
+    ("pendulum Tsit5", facts("pendulum", solver="tsit5", B=M22), (LEAN, 2, 256, 0, 0, 0, "sim_ahead_kernel (V=2)")),
+    ("pendulum RK4 keeps four", facts("pendulum", solver="rk4", B=M22), (LEAN, 4, 256, 0, 0, 0, "sim_ahead_kernel (V=4)")),
+    # row_sync 0 / 1 / 2
+    ("row_sync 2", facts(envs_per_lane=1), (LEAN, 1, 256, 2, 0, 0, "sim_ahead_kernel (V=1)")),
+    ("row_sync 1: ragged workgroup", facts(B=M17 + 1000, envs_per_lane=1), (LEAN, 1, 256, 1, 0, 0, "sim_ahead_kernel (V=1)")),
+    ("row_sync 1: misaligned trajectory", facts(al_straj=4), (LEAN, 1, 256, 1, 0, 0, "sim_ahead_kernel (V=1)")),
+    ("row_sync 0: gym outputs", facts(envs_per_lane=1, gym=1), (GENERAL, 1, 256, 0, 0, 0, "sim_ahead_kernel (general)")),
+    ("row_sync 0: small batch", facts(B=M17 - 256, envs_per_lane=1), (LEAN, 1, 256, 0, 0, 0, "sim_ahead_kernel (V=1)")),
+    # the lean gym form stores V * TW = 4 truncated bytes per lane as one dword: `truncated` must be 4-byte aligned
+    ("pendulum fp64 gym, truncated 2 bytes off", facts(dtype=F64, B=M17, K=5, gym=1, envs_per_lane=2, al_truncated=2),
+     (GENERAL, 1, 256, 0, 0, 0, "sim_ahead_kernel (general)")),
+    ("pendulum fp64 gym, truncated aligned", facts(dtype=F64, B=M17, K=5, gym=1, envs_per_lane=2, al_truncated=4),
+     (LEAN_GYM, 2, 256, 0, 0, 0, "sim_ahead_kernel (lean, gym outputs)")),
+    ("pendulum fp64 gym, odd TW: 2-byte flags suffice", facts(dtype=F64, B=M17, gym=1, n_control=1, envs_per_lane=2, al_truncated=2),
+     (LEAN_GYM, 2, 256, 0, 1, 0, "sim_ahead_kernel (lean, gym outputs)")),
+    ("PMSM fp32 gym, truncated 2 bytes off", facts("pmsm", gym=1, al_truncated=2), (GENERAL, 1, 256, 0, 0, 0, "sim_ahead_kernel (general)")),
+]
+
+# the shapes behind the last_launch() assertions of tests/test_gpu_*.py
+for name, dtype in (("pendulum", F64), ("pmsm", F64), ("cartpole", F64)):
+    K = 1000 if name == "pmsm" else 10000
+    CASES.append((f"env_major_ring fixture {name}", facts(name, dtype, B=64, K=K, action_layout=EM_L, traj_layout=EM_L, env_major_mode=3),
+                  (EMR, 1, 64, 0, 0, 16 if name == "pendulum" else 8, "sim_ahead_emr_kernel")))
+for dtype, P in ((F32, 16), (F64, 8)):
+    for sem in (0, 1):
+        for st in (0, 1):
+            CASES.append((f"env_major_ring pmsm 65536 {dtype} {sem} {st}",
+                          facts("pmsm", dtype, B=65536, K=64, semantics=sem, state_traj=st, action_layout=EM_L, traj_layout=EM_L),
+                          (EMR, 1, 64, 0, 0, P, "sim_ahead_emr_kernel")))
+for name, dtype, K in (("pmsm", F64, 40), ("pmsm", F32, 40), ("fluid_tank", F32, 64), ("pendulum", F64, 48), ("mass_spring_damper", F32, 16)):
+    for al, nc in ((16, 0), (128, 1)):
+        V = 16 // dtype
+        CASES.append((f"fused_actions {name} {dtype} {al} {nc}", facts(name, dtype, B=4096, K=K, action_layout=EM_L, al_actions=al, n_control=nc,
+                                                                    envs_per_lane=V), (AEM, V, 256, 0, nc > 0, 0, "sim_ahead_kernel (row-major actions fused)")))
+for dtype, solver in ((F32, "euler"), (F32, "tsit5"), (F64, "euler"), (F64, "rk4")):
+    V = 16 // dtype
+    for nc in (0, 3):
+        CASES.append((f"gym pmsm {dtype} {solver} {nc} lean", facts("pmsm", dtype, solver, B=2048, K=37, gym=1, n_control=nc, envs_per_lane=V),
+                      (LEAN_GYM, V, 256, 0, nc > 0, 0, "sim_ahead_kernel (lean, gym outputs)")))
+        CASES.append((f"gym pmsm {dtype} {solver} {nc} general", facts("pmsm", dtype, solver, B=2048, K=37, gym=1, n_control=nc, envs_per_lane=1),
+                      (GENERAL, 1, 256, 0, 0, 0, "sim_ahead_kernel (general)")))
+for name, nc in (("pendulum", 1), ("pendulum", 2), ("mass_spring_damper", 1), ("cartpole", 3), ("acrobot", 4), ("fluid_tank", 1), ("fluid_tank", 0)):
+    for dtype, solver in ((F32, "euler"), (F32, "rk4"), (F64, "euler"), (F64, "tsit5")):
+        V = 16 // dtype
+        wide = not (dtype == F64 and solver != "euler" and name in ("cartpole", "acrobot"))
+        CASES.append((f"gym {name} {nc} {dtype} {solver}", facts(name, dtype, solver, B=1024, K=29, gym=1, n_control=nc, envs_per_lane=V),
+                      (LEAN_GYM, V, 256, 0, nc > 0, 0, "sim_ahead_kernel (lean, gym outputs)") if wide else
+                      (GENERAL, 1, 256, 0, 0, 0, "sim_ahead_kernel (general)")))
+CASES += [
+    ("gym acrobot RK4 2^18 default", facts("acrobot", solver="rk4", B=M18, K=12, gym=1, n_control=2), (GENERAL, 1, 256, 0, 0, 0, "sim_ahead_kernel (general)")),
+    ("gym acrobot RK4 2^18 forced", facts("acrobot", solver="rk4", B=M18, K=12, gym=1, n_control=2, envs_per_lane=4),
+     (LEAN_GYM, 4, 256, 0, 1, 0, "sim_ahead_kernel (lean, gym outputs)")),
+    ("gym acrobot Euler 2^18 default", facts("acrobot", B=M18, K=12, gym=1, n_control=2), (LEAN_GYM, 4, 256, 0, 1, 0, "sim_ahead_kernel (lean, gym outputs)")),
+    ("row_sync per-env properties", facts("pmsm", B=M17 + 1000, K=12, per_env_props=1), (GENERAL, 1, 256, 1, 0, 0, "sim_ahead_kernel (general)")),
+    ("row_sync control + per-env + gym", facts("cartpole", B=M17, K=12, per_env_props=1, n_control=2, gym=1),
+     (GENERAL, 1, 256, 0, 0, 0, "sim_ahead_kernel (general)")),
+    ("row_sync forced wide", facts("pmsm", B=M17, K=10, envs_per_lane=4), (LEAN, 4, 256, 0, 0, 0, "sim_ahead_kernel (V=4)")),
+    ("wide gym msd", facts("mass_spring_damper", B=M20, K=9, gym=1, n_control=1), (LEAN_GYM, 4, 1024, 0, 1, 0, "sim_ahead_kernel (lean, gym outputs, 1024 threads)")),
+    ("wide gym tank", facts("fluid_tank", B=M20, K=9, gym=1), (LEAN_GYM, 4, 1024, 0, 0, 0, "sim_ahead_kernel (lean, gym outputs, 1024 threads)")),
+    ("fp64 pendulum gym stays narrow", facts(dtype=F64, B=M20, K=4, gym=1, n_control=1), (LEAN_GYM, 2, 256, 0, 1, 0, "sim_ahead_kernel (lean, gym outputs)")),
+    ("wide control columns", facts(B=M20, K=7, n_control=2), (LEAN, 4, 1024, 0, 1, 0, "sim_ahead_kernel (V=4, 1024 threads)")),
+    ("control columns one per lane", facts(B=M20, K=7, n_control=2, envs_per_lane=1), (LEAN, 1, 256, 2, 1, 0, "sim_ahead_kernel (V=1)")),
+]
+for which in ("al_state_io", "al_straj", "al_obs", "al_refs"):
+    CASES.append((f"gym misaligned {which}", facts(B=M17, K=5, gym=1, n_control=1, envs_per_lane=4, **{which: 4}),
+                  (GENERAL, 1, 256, 0, 0, 0, "sim_ahead_kernel (general)")))
+CASES.append(("gym aligned", facts(B=M17, K=5, gym=1, n_control=1, envs_per_lane=4), (LEAN_GYM, 4, 256, 0, 1, 0, "sim_ahead_kernel (lean, gym outputs)")))
+
+
+@pytest.fixture(scope="module")
+def planner(tmp_path_factory):
+    if CXX is None:
+        pytest.skip("no host C++ compiler")
+    d = tmp_path_factory.mktemp("sim_plan")
+    src, exe = d / "driver.cpp", d / "driver"
+    src.write_text(DRIVER)
+    subprocess.run([CXX, "-std=c++17", "-O1", "-Wall", "-Werror", "-I", CSRC, str(src), "-o", str(exe)], check=True)
+    rows = [" ".join(str(f[n]) for n in FIELDS) for _, f, _ in CASES]
+    out = subprocess.run([str(exe)], input="\n".join(rows) + "\n", capture_output=True, text=True, check=True).stdout.splitlines()
+    assert len(out) == len(CASES)
+    return dict(zip((c[0] for c in CASES), out))
+
+
+@pytest.mark.parametrize("case", CASES, ids=[c[0] for c in CASES])
+def test_plan(planner, case):
+    name, _, (form, V, threads, row_sync, split, period, launch) = case
+    nums, got_name = planner[name].split("|")
+    f, ws, v, t, rs, _lds, sp, p = map(int, nums.split())
+    assert (f, v, t, rs, sp, p, got_name) == (form, V, threads, row_sync, int(split), period, launch)
+    assert ws == (launch.startswith("transposition"))
+
+
+def test_every_form_is_covered():
+    assert {c[2][0] for c in CASES} == {GENERAL, LEAN, LEAN_GYM, AEM, EM, EM_GENERAL, EMR}
