@@ -218,7 +218,14 @@ int excenv_sim_ahead_ws(int env, int solver, int dtype, int64_t B, int64_t K, in
                         const excenv_launch_opts_t* opts, void* stream) {
   if (int rc = check_common("excenv_sim_ahead", env, solver, dtype, B)) return rc;
   if (K < 0 || substeps < 1) { set_error("excenv_sim_ahead: bad K=%lld or substeps=%d", (long long)K, substeps); return EXCENV_EINVAL; }
-  if (semantics != EXCENV_SEM_STEP && semantics != EXCENV_SEM_AHEAD) { set_error("excenv_sim_ahead: bad semantics %d", semantics); return EXCENV_EINVAL; }
+  if (semantics != EXCENV_SEM_STEP && semantics != EXCENV_SEM_AHEAD && semantics != EXCENV_SEM_AHEAD_ACCUMULATED_T) {
+    set_error("excenv_sim_ahead: bad semantics %d", semantics);
+    return EXCENV_EINVAL;
+  }
+  if (semantics == EXCENV_SEM_AHEAD_ACCUMULATED_T && K >= ((int64_t)1 << 30)) {  // the clock's action rows are 32-bit (sim_clock.hpp)
+    set_error("excenv_sim_ahead: EXCENV_SEM_AHEAD_ACCUMULATED_T needs K < 2^30 (got %lld)", (long long)K);
+    return EXCENV_EUNSUPPORTED;
+  }
   if (action_layout < EXCENV_LAYOUT_ENV_MAJOR || action_layout > EXCENV_LAYOUT_TILED ||
       traj_layout < EXCENV_LAYOUT_ENV_MAJOR || traj_layout > EXCENV_LAYOUT_TILED) {
     set_error("excenv_sim_ahead: bad layout id");

@@ -159,7 +159,7 @@ static bool fill_props(KProps<T, M>& kp, const excenv_props_t* p) {
 }
 
 // Launch with dynamic LDS; above the default 64 KiB limit the kernel's attribute is raised first (gfx950: 160 KiB per CU).
-#define EXCENV_LAUNCH_DYN(KERNEL, GRID, BLOCK, LDS, STREAM, ARGS)                                                         \
+#define EXCENV_LAUNCH_DYN(KERNEL, GRID, BLOCK, LDS, STREAM, ...)                                                         \
   do {                                                                                                                   \
     bool excenv_attr_ok = true;                                                                                          \
     if ((LDS) > 64 * 1024) {                                                                                             \
@@ -172,7 +172,7 @@ static bool fill_props(KProps<T, M>& kp, const excenv_props_t* p) {
         excenv_attr_ok = false;                                                                                          \
       }                                                                                                                  \
     }                                                                                                                    \
-    if (excenv_attr_ok) hipLaunchKernelGGL(KERNEL, GRID, BLOCK, LDS, STREAM, ARGS);                                      \
+    if (excenv_attr_ok) hipLaunchKernelGGL(KERNEL, GRID, BLOCK, LDS, STREAM, __VA_ARGS__);                               \
   } while (0)
 
 // Dynamic LDS for the saturated model's tables: staged when they fit LDS (<= 150 KiB, leaving room for one workgroup).
@@ -354,13 +354,60 @@ static void launch_sim_v(const SimPlan& p, SimArgs<T, M> ka, size_t lds_pad, hip
 #undef EXCENV_SIM_LAUNCH
 }
 
+// EXCENV_SEM_AHEAD_ACCUMULATED_T: the forms sim_plan.hpp can pick for it — general (with / without the gym outputs' code), lean
+// V = 1 / 2 / 4 with and without state trajectories, the look-up model's LDS-table variants, the 1024-thread lean form where
+// sim_wide_ok. Never the row-major action windows, the lean gym outputs or the env-major kernels (launch_sim checks).
+template <class M, typename T, int SOLVER>
+static void launch_sim_acc_t(const SimPlan& p, SimArgs<T, M> ka, T acc_step, T acc_end, size_t lds_pad, hipStream_t stream) {
+  const size_t lds = lut_lds_bytes<T, M>(ka.kp, lds_pad);
+  const int64_t lanes = ka.B / p.V;
+  const dim3 grid((unsigned)((lanes + p.threads - 1) / p.threads)), block(p.threads);
+  constexpr int VA = 16 / (int)sizeof(T);
+  if constexpr (sim_wide_ok(M::ID, (int)sizeof(T), SOLVER, M::HAS_LUT)) {
+    if (p.form == SIM_LEAN && p.threads == WIDE_THREADS) {
+      if (ka.straj[0] == nullptr) EXCENV_LAUNCH_DYN((sim_ahead_acc_t_kernel<M, T, SOLVER, false, VA, 0, false, WIDE_THREADS>), grid, block, lds, stream, ka, acc_step, acc_end);
+      else EXCENV_LAUNCH_DYN((sim_ahead_acc_t_kernel<M, T, SOLVER, false, VA, 1, false, WIDE_THREADS>), grid, block, lds, stream, ka, acc_step, acc_end);
+      return;
+    }
+  }
+#define EXCENV_ACC_LAUNCH(GEN, VV, ST)                                                                                        \
+  do {                                                                                                                        \
+    if constexpr (M::HAS_LUT) {                                                                                               \
+      if (ka.kp.lut_lds) {                                                                                                    \
+        EXCENV_LAUNCH_DYN((sim_ahead_acc_t_kernel<M, T, SOLVER, GEN, VV, ST, true>), grid, block, lds, stream, ka, acc_step, acc_end);           \
+        return;                                                                                                               \
+      }                                                                                                                       \
+    }                                                                                                                         \
+    EXCENV_LAUNCH_DYN((sim_ahead_acc_t_kernel<M, T, SOLVER, GEN, VV, ST, false>), grid, block, lds, stream, ka, acc_step, acc_end);             \
+    return;                                                                                                                   \
+  } while (0)
+  if (p.form == SIM_GENERAL) {
+    if (ka.truncated == nullptr) EXCENV_ACC_LAUNCH(true, 1, -2);
+    EXCENV_ACC_LAUNCH(true, 1, -1);
+  }
+  if (ka.straj[0] == nullptr) {
+    if constexpr (sizeof(T) == 4) {
+      if (p.V == 4) EXCENV_ACC_LAUNCH(false, 4, 0);
+    }
+    if (p.V == 2) EXCENV_ACC_LAUNCH(false, 2, 0);
+    EXCENV_ACC_LAUNCH(false, 1, 0);
+  }
+  if constexpr (sizeof(T) == 4) {
+    if (p.V == 4) EXCENV_ACC_LAUNCH(false, 4, 1);
+  }
+  if (p.V == 2) EXCENV_ACC_LAUNCH(false, 2, 1);
+  EXCENV_ACC_LAUNCH(false, 1, 1);
+#undef EXCENV_ACC_LAUNCH
+}
+
 // Validates the call, packs SimArgs and launches the form sc.plan names
 template <class M, typename T> static int launch_sim(const SimCall& sc) {
   SimArgs<T, M> ka;
   std::memset(&ka, 0, sizeof(ka));
   fill_props<T, M>(ka.kp, sc.props);
   double coef;
-  if (int rc = pmsm_coef<M>(sc.props, sc.env_tau, &coef, sc.semantics == EXCENV_SEM_AHEAD)) return rc;
+  const bool acc_t = sc.semantics == EXCENV_SEM_AHEAD_ACCUMULATED_T;  // AHEAD-structured like EXCENV_SEM_AHEAD
+  if (int rc = pmsm_coef<M>(sc.props, sc.env_tau, &coef, sc.semantics != EXCENV_SEM_STEP)) return rc;
   if (M::IS_PMSM && sc.substeps != 1) {
     set_error("PMSM: obs_stepsize must equal action_stepsize (reference pmsm_env.py:787)");
     return EXCENV_EUNSUPPORTED;
@@ -437,6 +484,11 @@ template <class M, typename T> static int launch_sim(const SimCall& sc) {
   }
 
   const SimPlan& p = sc.plan;
+  if (acc_t && (!p.acc_t || p.form == SIM_EMR || p.form == SIM_EM || p.form == SIM_EM_GENERAL || p.form == SIM_AEM ||
+                p.form == SIM_LEAN_GYM)) {  // sim_plan.hpp never plans these for it: the kernels have no accumulated-time form
+    set_error("excenv_sim_ahead: internal error: plan '%s' for EXCENV_SEM_AHEAD_ACCUMULATED_T", plan_name(p));
+    return EXCENV_EINVAL;
+  }
   if constexpr (emr_supported(M::HAS_LUT)) {
     if (p.form == SIM_EMR) {  // register-ring form (kernels_emr.hpp): whole-line stores, lanes p.period environments apart
       SimArgs<T, M> kr = ka;
@@ -497,9 +549,12 @@ template <class M, typename T> static int launch_sim(const SimCall& sc) {
     }
   }
   const size_t lds_pad = (size_t)sc.lds_pad + p.row_lds;
+  // the accumulated-time clock's action step and end time, folded in double as oracle_body.inc does
+  const T acc_step = (T)(sc.obs_stepsize * (double)sc.substeps), acc_end = (T)((sc.obs_stepsize * (double)sc.substeps) * (double)sc.K);
 #define EXCENV_SIM_CASE(SOLV)                                                                \
   case SOLV:                                                                                 \
-    if (sc.semantics == EXCENV_SEM_AHEAD) launch_sim_v<M, T, SOLV, true>(p, ka, lds_pad, sc.stream); \
+    if (acc_t) launch_sim_acc_t<M, T, SOLV>(p, ka, acc_step, acc_end, lds_pad, sc.stream);   \
+    else if (sc.semantics == EXCENV_SEM_AHEAD) launch_sim_v<M, T, SOLV, true>(p, ka, lds_pad, sc.stream); \
     else launch_sim_v<M, T, SOLV, false>(p, ka, lds_pad, sc.stream);                         \
     break;
   switch (sc.solver) {

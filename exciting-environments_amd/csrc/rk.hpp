@@ -173,7 +173,9 @@ __device__ __forceinline__ void env_advance_raw(T (&st)[M::S], const T (&a)[M::A
   } else {
     u[0] = denormalize(a[0], c.amin[0], c.amax[0]);
   }
-  // the action of stages with c_i == 1: row k1 (== k inside an action's sub-steps), read only when that stage is reached
+  // the action of stages with c_i == 1: row k1 (== k inside an action's sub-steps, and on the accumulated-time clock wherever its row
+  // stays), read only when that stage is reached. Stages with 0 < c_i < 1 read row k on every clock (the oracle's restatement; literal
+  // diffrax would look them up at t_prev + c_i dt)
   auto u1_of = [&](T (&u1)[M::A]) __attribute__((always_inline)) {
     if constexpr (M::IS_PMSM) {
       if (dead) {

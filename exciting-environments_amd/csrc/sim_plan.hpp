@@ -119,10 +119,15 @@ struct SimPlan {
   int row_sync, row_lds;  // kernels.hpp row_sync: 0 off, 1 barrier per row, 2 rows leave through LDS (row_lds bytes)
   bool split_control;  // the control columns are filled by control_fill_kernel behind the trajectory kernel
   int64_t period;      // SIM_EMR: environments between the lanes of a wave
+  bool acc_t = false;  // EXCENV_SEM_AHEAD_ACCUMULATED_T: the accumulated-time instantiations of GENERAL / LEAN (kernels.hpp ACC_T)
 };
 
 namespace plan_detail {
 constexpr int vmax(const SimFacts& f) { return 16 / f.elem; }
+// EXCENV_SEM_AHEAD_ACCUMULATED_T: the action row is not step / substeps (it stays or jumps by two in some steps), so the forms that
+// assume one row per step — the row-major action windows (AEM), the fused env-major kernels (EM, EM_GENERAL, EMR) — and the lean gym
+// outputs have no instantiation for it; everything else is planned exactly as for EXCENV_SEM_AHEAD.
+constexpr bool acc_t(const SimFacts& f) { return f.semantics == EXCENV_SEM_AHEAD_ACCUMULATED_T; }
 // The lane width the widest-only forms (AEM, lean gym outputs) need is the one the call would take anyway
 constexpr bool takes_widest(const SimFacts& f) {
   int want = f.envs_per_lane > 0 ? f.envs_per_lane : (widest_form_pays(f.B, vmax(f)) ? vmax(f) : 1);
@@ -135,7 +140,7 @@ constexpr bool takes_widest(const SimFacts& f) {
 // transposition pass in front of the launch. Control columns are filled behind it (control_fill_kernel reads every reference).
 constexpr bool reads_row_major_actions(const SimFacts& f) {
   const int vm = vmax(f);
-  if ((f.flags & EXCENV_OPT_NO_FUSED_ACTIONS) || f.lut || f.per_env_props || f.gym || !f.refs_given || f.al_obs < 16) return false;
+  if ((f.flags & EXCENV_OPT_NO_FUSED_ACTIONS) || acc_t(f) || f.lut || f.per_env_props || f.gym || !f.refs_given || f.al_obs < 16) return false;
   if (f.action_layout != EXCENV_LAYOUT_ENV_MAJOR || f.traj_layout != EXCENV_LAYOUT_LANE_MAJOR) return false;
   if (f.K < 1 || !aem_fits(f.A, f.elem) || (f.K * f.A) % vm != 0) return false;  // whole 16-byte pieces per row
   if ((f.B % (64 * vm)) != 0) return false;  // whole waves: the lanes of a wave fetch action windows for each other
@@ -145,7 +150,7 @@ constexpr bool reads_row_major_actions(const SimFacts& f) {
 }
 // Both layouts env-major, substeps == 1, no gym trajectories, the time tile fits LDS, the action array made of whole 16-byte pieces
 constexpr bool fused_env_major(const SimFacts& f) {
-  return f.B > 0 && f.K > 0 && f.al_obs >= 16 && f.al_actions >= 16 && (f.B * f.K * f.A * f.elem) % 16 == 0 &&
+  return !acc_t(f) && f.B > 0 && f.K > 0 && f.al_obs >= 16 && f.al_actions >= 16 && (f.B * f.K * f.A * f.elem) % 16 == 0 &&
          f.env_major_mode != 1 && f.action_layout == EXCENV_LAYOUT_ENV_MAJOR && f.traj_layout == EXCENV_LAYOUT_ENV_MAJOR &&
          f.substeps == 1 && !f.gym && em_lds_elems(f.elem, f.S, f.O) * f.elem <= 150 * 1024;
 }
@@ -156,7 +161,7 @@ constexpr SimPlan plan_env_major(const SimFacts& f) {
   // trajectory arrays, action rows of whole 16-byte pieces (fetched as 64-byte windows by LDS-direct loads) and enough
   // environments to fill waves whose lanes are P environments apart.
   if ((f.env_major_mode == 0 || f.env_major_mode == 3) && !general && emr_supported(f.lut)) {
-    const int64_t P = emr_period(f.K, emr_rows(f.S, f.env == EXCENV_PMSM, f.semantics == EXCENV_SEM_AHEAD, f.elem));
+    const int64_t P = emr_period(f.K, emr_rows(f.S, f.env == EXCENV_PMSM, f.semantics != EXCENV_SEM_STEP, f.elem));
     if (f.al_obs >= 128 && f.al_straj >= 128 && (f.env_major_mode == 3 || f.B >= 16 * EM_LANES * P) &&
         (f.K * f.A * f.elem) % 16 == 0 && f.al_actions >= 16 &&
         EM_LANES * P * (f.K + 1) * f.O * (int64_t)f.elem < ((int64_t)1 << 31))  // 32-bit lane offsets
@@ -174,7 +179,7 @@ constexpr SimPlan plan_lane_major(const SimFacts& f) {
   // the arrays allow its vector accesses: truncated V * TW bytes per lane, as dwords aligned to 4 bytes when that is a multiple of 4,
   // else to 2 (kernels.hpp store_flag_bytes). Anything else takes the general kernel.
   const int TW = (f.env == EXCENV_PMSM || f.env == EXCENV_FLUID_TANK) ? 1 : f.O + f.n_control;
-  const bool lean_gym = f.gym && !f.per_env_props && !f.lut && f.n_control <= f.S && lm_a && lm_t && (f.B % VMAX) == 0 &&
+  const bool lean_gym = f.gym && !acc_t(f) && !f.per_env_props && !f.lut && f.n_control <= f.S && lm_a && lm_t && (f.B % VMAX) == 0 &&
                         takes_widest(f) && states16 && f.al_actions >= 16 && f.al_obs >= 16 && f.al_reward >= 16 &&
                         f.al_terminated >= VMAX && f.al_truncated >= ((VMAX * TW) % 4 == 0 ? 4 : 2) &&
                         (f.n_control == 0 || (f.refs_given && f.al_refs >= 16)) &&
@@ -253,14 +258,25 @@ constexpr SimPlan sim_plan(const SimFacts& f) {
     w.flags = 0;
     SimPlan p = plan_lane_major(w);
     p.via_workspace = true;
+    p.acc_t = acc_t(f);
     return p;
   }
-  return plan_lane_major(f);
+  SimPlan p = plan_lane_major(f);
+  p.acc_t = acc_t(f);
+  return p;
 }
 // What excenv_last_launch() reports for a plan
 constexpr const char* plan_name(const SimPlan& p) {
-  if (p.via_workspace) return "transposition workspace + sim_ahead_kernel";
   const bool wide = p.threads == WIDE_THREADS;
+  if (p.acc_t) {  // GENERAL / LEAN only (sim_plan)
+    if (p.via_workspace) return "transposition workspace + sim_ahead_kernel (accumulated t)";
+    if (p.form == SIM_GENERAL) return "sim_ahead_kernel (general, accumulated t)";
+    if (p.form != SIM_LEAN) return "sim_ahead_kernel (unsupported form, accumulated t)";
+    if (p.V == 1) return "sim_ahead_kernel (V=1, accumulated t)";
+    if (p.V == 2) return wide ? "sim_ahead_kernel (V=2, 1024 threads, accumulated t)" : "sim_ahead_kernel (V=2, accumulated t)";
+    return wide ? "sim_ahead_kernel (V=4, 1024 threads, accumulated t)" : "sim_ahead_kernel (V=4, accumulated t)";
+  }
+  if (p.via_workspace) return "transposition workspace + sim_ahead_kernel";
   switch (p.form) {
     case SIM_GENERAL: return "sim_ahead_kernel (general)";
     case SIM_LEAN_GYM: return wide ? "sim_ahead_kernel (lean, gym outputs, 1024 threads)" : "sim_ahead_kernel (lean, gym outputs)";

@@ -16,6 +16,9 @@ MAX_STATE, MAX_ACTION, MAX_STATIC, MAX_CONTROL = 8, 2, 9, 8
 LAYOUT_ENV_MAJOR, LAYOUT_LANE_MAJOR, LAYOUT_TILED = 0, 1, 2
 TILE = 1024  # EXCENV_TILE
 SEM_STEP, SEM_AHEAD = 0, 1
+SEM_AHEAD_ACCUMULATED_T = 2  # opt-in: diffrax's accumulated-time clock as the CPU oracle restates it (include/excenv.h)
+# CoreEnvironment.sim_ahead_semantics -> excenv_semantics_t
+SEMANTICS = {"step": SEM_STEP, "ahead": SEM_AHEAD, "ahead_accumulated_t": SEM_AHEAD_ACCUMULATED_T}
 F32, F64 = 0, 1
 ABI_VERSION = 7
 

@@ -70,7 +70,7 @@ class TrajectoryLaunchMixin:
         else:
             raise ValueError(f"traj_layout must be 'lane_major', 'env_major' or 'tiled', got {self.traj_layout!r}")
         last = [torch.empty(B, dtype=self.dtype, device=self.device) for _ in range(S)]
-        sem = {"ahead": _native.SEM_AHEAD, "step": _native.SEM_STEP}[self.sim_ahead_semantics]
+        sem = self._semantics_id
         workspace = None
         if self.env_major_workspace and B > 0 and _native.LAYOUT_ENV_MAJOR in (a_layout, t_layout):
             # env-major (row-major) buffers: let the library transpose through a scratch buffer instead of issuing
@@ -127,7 +127,7 @@ class TrajectoryLaunchMixin:
             if ws_bytes > 0:
                 ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)  # stream-ordered: free to die when this function returns
                 ws_ptr = ws.data_ptr()
-        sem = _native.SEM_AHEAD if self.sim_ahead_semantics == "ahead" else _native.SEM_STEP
+        sem = self._semantics_id
         st_in_ptrs = _native._ptrs(st_in)
 
         def launch(o_ptr, t_ptrs, l_ptrs):
@@ -175,11 +175,13 @@ class TrajectoryLaunchMixin:
             # the launch fuses only when every state array allows 16-byte accesses as well (launch.hpp: vec_ok); the output arrays
             # made below always do. A "fused" answer for a call that then does not fuse would skip the workspace and drop the call
             # to the generic-stride read of the actions — correct, but far slower than the transposition it replaced.
+            # (the query describes the step and ahead semantics: accumulated-time calls never fuse, so they always get the workspace)
             aligned = all(t.data_ptr() % 16 == 0 for t in st_in)
+            acc_t = self._semantics_id == _native.SEM_AHEAD_ACCUMULATED_T
             fk = (B, K, sub, len(self.control_state), actions.data_ptr() % 16, id(props), bool(want_gym), aligned,
-                  None if opts is None else (opts.envs_per_lane, opts.flags))
+                  None if opts is None else (opts.envs_per_lane, opts.flags), self._semantics_id)
             if self._fused_actions_cache is None or self._fused_actions_cache[0] != fk:
-                self._fused_actions_cache = (fk, aligned and _native.sim_ahead_fuses_actions(
+                self._fused_actions_cache = (fk, aligned and not acc_t and _native.sim_ahead_fuses_actions(
                     self.ENV_ID, self._solver.id, dt, B, K, props, len(self.control_state), bool(want_gym), a_layout,
                     _native.LAYOUT_LANE_MAJOR, actions.data_ptr(), opts))
             if self.env_major_workspace and not self._fused_actions_cache[1]:
@@ -193,7 +195,7 @@ class TrajectoryLaunchMixin:
         st_views = None
         traj_ptrs = None
         ws_ptr = None
-        sem = _native.SEM_AHEAD if self.sim_ahead_semantics == "ahead" else _native.SEM_STEP
+        sem = self._semantics_id
         st_in_ptrs = _native._ptrs(st_in)
 
         gym_out = gym_ref = None

@@ -108,7 +108,8 @@ class CoreEnvironment(TrajectoryLaunchMixin, ABC):
         # "lane_major": trajectories are [K+1, O, B] buffers returned as [B, K+1, O] views (coalesced kernel
         # accesses); "env_major": contiguous [B, K+1, O] like the reference's row-major jnp arrays.
         self.traj_layout = "lane_major"
-        # "ahead": structure of the reference's _ode_solver_simulate_ahead; "step": K exact `step`s.
+        # "ahead": structure of the reference's _ode_solver_simulate_ahead; "step": K exact `step`s; "ahead_accumulated_t": opt-in,
+        # "ahead" on diffrax's accumulated-time clock (see the sim_ahead_semantics property)
         self.sim_ahead_semantics = "ahead"
         # env-major (row-major) buffers, three bit-identical paths: fused LDS time-tile kernel (default when both actions and
         # trajectories are env-major), else transposition through a scratch workspace, else the generic-stride kernel
@@ -847,10 +848,32 @@ class CoreEnvironment(TrajectoryLaunchMixin, ABC):
             **{n: t.reshape(()) for n, t in zip(self.STATE_FIELDS, last)}), additions=self._additions((), True))
         return obs[0], states, last_state
 
+    @property
+    def sim_ahead_semantics(self):
+        """What `vmap_sim_ahead` / `sim_ahead` compute (include/excenv.h excenv_semantics_t):
+        "ahead" (default): the structure of the reference's _ode_solver_simulate_ahead with steps of exactly obs_stepsize and the
+        action of step n at index n // substeps — the documented contract; "step": n exact `step`s; "ahead_accumulated_t"
+        (opt-in; an oracle restatement of diffrax's loop, unpinned): "ahead" with the step times accumulated in the working
+        precision as diffrax does, the step size tnext - tprev and the action looked up at int(t / action_stepsize) — what the
+        reference returns where that rounding moves the index (most steps of an fp32 chunk). K must be below 2^30."""
+        return self._sim_ahead_semantics
+
+    @sim_ahead_semantics.setter
+    def sim_ahead_semantics(self, value):
+        if value not in _native.SEMANTICS:
+            raise ValueError(f"sim_ahead_semantics must be one of {sorted(_native.SEMANTICS)}, got {value!r}")
+        self._sim_ahead_semantics = value
+        self._semantics_id = _native.SEMANTICS[value]
+
     def vmap_sim_ahead(self, init_state, actions, obs_stepsize, action_stepsize, return_rew_trunc_term=False, out=None):
         """Trajectories of all batch_size environments in one persistent kernel launch (core_env.py:571-616):
         actions (batch_size, n_action_steps, action_dim) -> observations (batch_size, n+1, obs_dim), states with
         leaves (batch_size, n+1), last_state with leaves (batch_size,).
+
+        env.sim_ahead_semantics selects the clock: "ahead" (default) steps by exactly obs_stepsize and reads action n // substeps;
+        "ahead_accumulated_t" (opt-in) accumulates the step times in the working precision like diffrax and reads the action at
+        int(t / action_stepsize) — an oracle restatement of diffrax's loop, not pinned against diffrax itself. Stages with
+        0 < c_i < 1 (RK4, Tsit5) read the row of the step's start there, where diffrax would look at tprev + c_i * dt.
 
         return_rew_trunc_term=True (extension): the same launch also evaluates what
         vmap_generate_rew_trunc_term_ahead(states, actions) would (core_env.py:618-647) and the call returns

@@ -72,10 +72,21 @@ typedef enum { EXCENV_LAYOUT_ENV_MAJOR = 0, EXCENV_LAYOUT_LANE_MAJOR = 1, EXCENV
  *                      ODE state is carried un-wrapped / un-clipped, post-processing is applied to the SAVED
  *                      rows only, PMSM clips all actions with the predicted angle eps0 + k*tau*omega, and RK
  *                      stages with c_i == 1 read action k+1 (core_env.py:435-439). Step size is exactly
- *                      obs_stepsize and the action index is exactly floor(step / substeps) (diffrax's
- *                      accumulated-time rounding is deliberately not reproduced).
+ *                      obs_stepsize and the action index is exactly floor(step / substeps): the documented
+ *                      contract, and the default of the Python API.
+ *   EXCENV_SEM_AHEAD_ACCUMULATED_T : opt-in; EXCENV_SEM_AHEAD on diffrax's accumulated-time clock as the CPU
+ *                      oracle restates it (unpinned: not checked against diffrax itself). (t_prev, t_next) are
+ *                      carried in the working precision from (0, obs_stepsize); each solver step has the size
+ *                      t_next - t_prev, then (t_prev, t_next) = (t_next, 2 t_next - t_prev) with t_next snapped to
+ *                      t_end = obs_stepsize * substeps * K within 1e-6 (fp32) / 1e-10 (fp64). The first stage and
+ *                      stages with 0 < c_i < 1 read action int(t_prev / (obs_stepsize * substeps)), stages with
+ *                      c_i == 1 action int(t_next / (obs_stepsize * substeps)), both clamped to [0, K - 1] (the
+ *                      reference's actions[int(t / action_stepsize)], pendulum_env.py:215-216). In fp32 the row
+ *                      differs from EXCENV_SEM_AHEAD's in most steps of a typical chunk. Known limit: literal
+ *                      diffrax evaluates stages with 0 < c_i < 1 at t_prev + c_i * dt (RK4 / Tsit5 only). K must be
+ *                      below 2^30. A library older than this value rejects it with EXCENV_EINVAL (same ABI version).
  */
-typedef enum { EXCENV_SEM_STEP = 0, EXCENV_SEM_AHEAD = 1 } excenv_semantics_t;
+typedef enum { EXCENV_SEM_STEP = 0, EXCENV_SEM_AHEAD = 1, EXCENV_SEM_AHEAD_ACCUMULATED_T = 2 } excenv_semantics_t;
 
 #define EXCENV_MAX_STATE 8
 #define EXCENV_MAX_ACTION 2
@@ -244,7 +255,8 @@ int excenv_sim_ahead_ws(int env, int solver, int dtype, int64_t B, int64_t K, in
  * trajectories (control columns are filled by a second small launch behind the lean kernel), the batch sizes that run
  * V = 16 / sizeof(dtype) environments per lane with B % (64 V) == 0, K * A * sizeof(dtype) a multiple of 16 and 16-byte aligned
  * actions. The answer assumes what the query cannot see: every control->reference[j] non-NULL, and the state_in, last_state,
- * state_traj and obs_traj arrays 16-byte aligned (as for every vectorised launch). */
+ * state_traj and obs_traj arrays 16-byte aligned (as for every vectorised launch). It describes EXCENV_SEM_STEP and
+ * EXCENV_SEM_AHEAD calls: under EXCENV_SEM_AHEAD_ACCUMULATED_T row-major actions are never fused. */
 int excenv_sim_ahead_fuses_actions(int env, int solver, int dtype, int64_t B, int64_t K, const excenv_props_t* props,
                                    int32_t n_control, int with_gym, int action_layout, int traj_layout, const void* actions,
                                    const excenv_launch_opts_t* opts);
