@@ -198,15 +198,7 @@ __device__ __forceinline__ void sincos_fast(float x, float& s, float& c);
 // code object instead of once per call site. Inlined, every sincos_t of a trajectory loop carried its own copy — the lean gym
 // loops of cart-pole / acrobot (20 call sites per half loop) were 80 KB, 130 KB after the guards became wave-uniform; with the
 // call they are 44 KB, register counts unchanged, no scratch (round 5, tools/loop_code_size.py). Never executed for |x| <= 65536.
-#ifndef EXCENV_SLOW_PATHS_NOINLINE
-#define EXCENV_SLOW_PATHS_NOINLINE 1
-#endif
-#if EXCENV_SLOW_PATHS_NOINLINE
-#define EXCENV_SLOW_FN __device__ __attribute__((noinline))
-#else
-#define EXCENV_SLOW_FN __device__ __forceinline__
-#endif
-EXCENV_SLOW_FN float2 sincos_lib(float x) { return make_float2(::sinf(x), ::cosf(x)); }
+__device__ __attribute__((noinline)) float2 sincos_lib(float x) { return make_float2(::sinf(x), ::cosf(x)); }
 __device__ __forceinline__ void sincos_t(float x, float& s, float& c) {
   sincos_fast(x, s, c);
   const bool big = !(xabs(x) <= 65536.0f);  // also NaN / inf

@@ -8,12 +8,6 @@
 
 namespace excenv {
 
-#ifndef EXCENV_NT_STORES
-#define EXCENV_NT_STORES 1
-#endif
-#ifndef EXCENV_PINGPONG
-#define EXCENV_PINGPONG 1  // bit 0: Euler, bit 1: RK4 / Tsit5 — K loop unrolled by two with ping-pong action registers
-#endif                      // (2-step prefetch distance, 2x loop code). Measured: +3.5 % Euler, -5 % Tsit5.
 // Deliberately broken builds for the self-test of the static guards (tools/isa_guards.py, tools/isa_guards_selftest.sh): bit 0 counts
 // one store too many in the hand-written wait of the action windows, bit 1 drops the LDS wait in front of the row barrier, bit 2
 // drops the wait state between the write of M0 and the LDS-direct load. Never set in a product build (static_assert in excenv_api.hip).
@@ -188,9 +182,8 @@ template <typename T, int V> __device__ __forceinline__ void store_v(T* p, const
   }
 }
 
-// Trajectory rows are written once and never read back by the kernel: optional streaming (nt) stores.
+// Trajectory rows are written once and never read back by the kernel: streaming (nt) stores.
 template <typename T, int V> __device__ __forceinline__ void store_stream(T* p, const T (&in)[V]) {
-#if EXCENV_NT_STORES
   if constexpr (V == 1) {
     *p = in[0];  // V == 1 also serves the env-major layout, whose scattered words must merge in L2: no nt
   } else {
@@ -200,9 +193,6 @@ template <typename T, int V> __device__ __forceinline__ void store_stream(T* p, 
     for (int j = 0; j < V; ++j) v[j] = in[j];
     __builtin_nontemporal_store(v, reinterpret_cast<NVT*>(p));
   }
-#else
-  store_v<T, V>(p, in);
-#endif
 }
 
 // Row-major row of N values per lane (obs[B][O], action[B][A]): widest power-of-two chunks up to 16 bytes.
@@ -475,14 +465,11 @@ template <typename T, int V> constexpr bool aem_shape_ok() { return V * (int)siz
   asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(SRC), "s"(M0V) : "memory", "m0");      \
   _Pragma("clang diagnostic pop")
 #endif
-#ifndef EXCENV_AEM_NP
-#define EXCENV_AEM_NP 4  // 16-byte pieces per window (64 bytes; V * NP KiB of LDS per wave)
-#endif
 constexpr int AEM_BLOCK_BYTES = 1024 + 16;  // one LDS-direct load instruction's 1 KiB + the bank skew
 // Pieces per window. 64-byte windows everywhere (same-session sweep over nine workloads, profiles/r04_rowmajor_actions_pmc.md: 32-byte windows
 // cost 3 ... 30 % more: two fabric requests per 64 bytes) except acrobot, whose registers already cap it at two workgroups per
 // CU and which gains 6 % from the smaller LDS footprint.
-template <class M> constexpr int aem_np() { return M::ID == EXCENV_ACROBOT ? 2 : EXCENV_AEM_NP; }
+template <class M> constexpr int aem_np() { return M::ID == EXCENV_ACROBOT ? 2 : 4; }
 template <class M, typename T, int V> constexpr size_t aem_lds_bytes() { return (size_t)(BLOCK / 64) * V * aem_np<M>() * AEM_BLOCK_BYTES; }
 
 // LGYM (round 4; lean, V * sizeof(T) == 16, not the look-up model): the reward / terminated / truncated trajectories of
@@ -499,7 +486,7 @@ template <class M, typename T, int V> constexpr size_t aem_lds_bytes() { return 
 // rewards that: pendulum Euler fp32 (C2) 3.98 -> 3.56 ms, MSD Euler 1.53 -> 1.43, tank 0.87 -> 0.81 in a same-buffers A/B
 // (tools/ab_same_buffers.py, profiles/r04_pattern_sweep.md). With more arithmetic per row (RK4 / Tsit5, cart-pole, acrobot, PMSM)
 // lockstep takes away the overlap of one wave's arithmetic with another's stores and the same change LOSES 2 ... 9 %: NT == BLOCK
-// there, no barrier. sim_threads<M, T>() (launch.hpp) is the rule.
+// there, no barrier. sim_wide_ok() (sim_plan.hpp) is the rule.
 // Register caps (the "amdgpu-waves-per-eu" lower bound: 512 / n registers per lane). The compiler does not weigh a wave per SIMD
 // against a few registers: when the math primitives were restructured in round 5 these instantiations went from 205 ... 254 to
 // 259 ... 294 registers — one wave per SIMD instead of two (acrobot's gym trajectories: 4.9 -> 6.0 ms). Everything else keeps the

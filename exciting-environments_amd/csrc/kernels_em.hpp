@@ -25,21 +25,16 @@
 
 namespace excenv {
 
-// TK (steps per flush window, EXCENV_EM_TK) and the LDS bytes per wave: em_tk / em_lds_elems in sim_plan.hpp.
+// TK (steps per flush window, EM_TK) and the LDS bytes per wave: em_tk / em_lds_elems in sim_plan.hpp.
 // Observation rows are written as non-temporal stores: complete lines that nothing reads back. The state leaves and the
 // action loads stay cacheable — non-temporal state stores measured -40 %, non-temporal action loads -30 %: the L2 merges
 // part of the state leaves' partial bursts and re-serves the action lines shared by consecutive tiles.
-static_assert((EXCENV_EM_TK & (EXCENV_EM_TK - 1)) == 0 && EXCENV_EM_TK >= 2 && EXCENV_EM_TK <= EM_LANES,
-              "EXCENV_EM_TK must be a power of two in [2, 64]");
+static_assert((EM_TK & (EM_TK - 1)) == 0 && EM_TK >= 2 && EM_TK <= EM_LANES, "EM_TK must be a power of two in [2, 64]");
 // One wave per workgroup: LDS instructions of a wave execute in issue order, so a value one lane wrote is visible to the lane
 // that reads it later in program order — no s_barrier and no s_waitcnt lgkmcnt(0) (which __syncthreads() implies) are needed,
 // only the compiler must not reorder the accesses.
 static_assert(EM_LANES == 64, "the fused env-major kernel relies on a single wave64 per workgroup");
 __device__ __forceinline__ void wave_sync() { asm volatile("" ::: "memory"); }
-
-#ifndef EXCENV_EM_DEBUG
-#define EXCENV_EM_DEBUG 0  // experiments only (results are wrong): 1 skip the observation stores, 2 skip the flush, 4 skip the action-line walk
-#endif
 
 template <class M, typename T, int SOLVER, bool AHEAD, bool BATCHED>
 __global__ void __launch_bounds__(EM_LANES) sim_ahead_em_kernel(const SimArgs<T, M> ka) {
@@ -176,7 +171,7 @@ __global__ void __launch_bounds__(EM_LANES) sim_ahead_em_kernel(const SimArgs<T,
           const unsigned ro = row_off[row];
           T v[VW];
           load_v<T, VW>(stage + p * VW, v);
-          if (!(EXCENV_EM_DEBUG & 1) && ro != 0xffffffffu) store_stream<T, VW>(wg_obs + ro * (unsigned)O + (unsigned)(piece * VW), v);
+          if (ro != 0xffffffffu) store_stream<T, VW>(wg_obs + ro * (unsigned)O + (unsigned)(piece * VW), v);
         }
       } else {
         T fs[S];
@@ -243,7 +238,7 @@ __global__ void __launch_bounds__(EM_LANES) sim_ahead_em_kernel(const SimArgs<T,
     // only has to outlast the stores of the PREVIOUS step's flush, not stores issued a few instructions ago.
     const int64_t k1 = (n + 1 < ka.K) ? n + 1 : ka.K - 1;
     const int64_t r1 = row0 + k1 * A;
-    if (!(EXCENV_EM_DEBUG & 4) && n < N && (r1 & ~(int64_t)(WPL - 1)) != cur_line) {
+    if (n < N && (r1 & ~(int64_t)(WPL - 1)) != cur_line) {
       park_line(park_from);
       cur_line += WPL;
       load_line(cur_line + WPL, load_into);
@@ -268,7 +263,6 @@ __global__ void __launch_bounds__(EM_LANES) sim_ahead_em_kernel(const SimArgs<T,
     // environments whose window ends with step n (or with the trajectory)
     const bool due = active && ((((my_ph + (unsigned)slot + 1u) % TK) == 0u) || n == N);
     unsigned long long mask = __ballot(due);
-    if (EXCENV_EM_DEBUG & 2) mask = 0;
     while (mask) flush_round(mask, n);
     if (n < N) {
       T a_nxt[A];

@@ -35,25 +35,6 @@ template <typename T, int W> struct EmrVec { typedef T type __attribute__((ext_v
 constexpr int EMR_ANP = 4;  // 16-byte pieces per action window (64 bytes, fetched by 4 adjacent lanes of one LDS-direct load)
 template <class M, typename T, bool AHEAD> constexpr size_t emr_lds_bytes() { return (size_t)EM_LANES * 128 + (size_t)EMR_ANP * AEM_BLOCK_BYTES; }
 
-#ifndef EXCENV_EMR_DEBUG
-#define EXCENV_EMR_DEBUG 0  // experiments only (results are wrong): 1 never walk to the next action line, 2 no flush, 4 flush without global stores
-#endif
-#ifndef EXCENV_EMR_ROW_UNROLL
-#define EXCENV_EMR_ROW_UNROLL 1  // observation rows evaluated together at flush time (models with more than two ring leaves)
-#endif
-#ifndef EXCENV_EMR_DEFER
-#define EXCENV_EMR_DEFER 1       // the observation rows of a flush as branch-free blocks of EXCENV_EMR_DEFER_ROWS rows (see flush)
-#endif
-#ifndef EXCENV_EMR_DEFER_ROWS
-#define EXCENV_EMR_DEFER_ROWS 4
-#endif
-#ifndef EXCENV_EMR_UNROLL_LINES
-#define EXCENV_EMR_UNROLL_LINES 0  // 1: the lines of a window unrolled — static ring indices instead of s_set_gpr_idx reads, 4 x the row code
-#endif
-#ifndef EXCENV_EMR_NT
-#define EXCENV_EMR_NT 1  // whole-run stores of the flush are non-temporal (plain stores: 10 ... 11 ms instead of 7 for the headline launch)
-#endif
-
 // ka.a_wg carries P (environments between consecutive lanes of a wave) on this path.
 template <class M, typename T, int SOLVER, bool AHEAD>
 __global__ void __launch_bounds__(EM_LANES) __attribute__((amdgpu_waves_per_eu(2))) sim_ahead_emr_kernel(const SimArgs<T, M> ka) {
@@ -191,15 +172,8 @@ __global__ void __launch_bounds__(EM_LANES) __attribute__((amdgpu_waves_per_eu(2
 #pragma unroll
         for (int q = 0; q < 4; ++q) load_v<T, VW>(xp + (pi * EM_LANES + ((g8 + q0 + q) ^ pi)) * VW, v[q]);
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-#if EXCENV_EMR_DEBUG & 4
-          asm volatile("" ::"v"(v[q][0]), "v"(v[q][VW - 1]), "v"(lane_off));
-#elif EXCENV_EMR_NT
+        for (int q = 0; q < 4; ++q)  // non-temporal: plain stores took 10 ... 11 ms instead of 7 for the headline launch
           store_stream<T, VW>(ubase + (q0 + q) * q_stride + lane_off, v[q]);
-#else
-          store_v<T, VW>(ubase + (q0 + q) * q_stride + lane_off, v[q]);
-#endif
-        }
       }
     } else {
 #pragma unroll
@@ -249,11 +223,7 @@ __global__ void __launch_bounds__(EM_LANES) __attribute__((amdgpu_waves_per_eu(2
     // observation lines: line l of the window holds rows [l * RPO, (l + 1) * RPO)
     const int po = lane % NPL;
     const unsigned lane_rows_o = (unsigned)((int64_t)P * (lane - po) * rowlen);
-#if EXCENV_EMR_UNROLL_LINES
-#pragma unroll
-#else
 #pragma unroll 1
-#endif
     for (int l = 0; l < NLO; ++l) {
       if ((l + 1) * RPO - 1 < s_lo || l * RPO > s_hi) continue;  // wave-uniform
       // the rows' observation values go into the transposition buffer piece by piece as they are produced (a whole line of them in
@@ -284,7 +254,7 @@ __global__ void __launch_bounds__(EM_LANES) __attribute__((amdgpu_waves_per_eu(2
         M::observe(fs, c, ob);
         put_row(t, ob);
       };
-      if constexpr (EXCENV_EMR_DEFER && observe_defer_ok<M, T>()) {
+      if constexpr (observe_defer_ok<M, T>()) {
         // Round 5: G rows as ONE straight-line block. A wave of this kernel carries one environment per lane, so a row's
         // generate_observation is one dependent chain (sin / cos -> ..., six normalisations) and the guards inside sincos_t /
         // InvDiv::div end basic blocks: unrolled rows could not interleave (round 4: two / four rows "together" measured flat).
@@ -292,7 +262,7 @@ __global__ void __launch_bounds__(EM_LANES) __attribute__((amdgpu_waves_per_eu(2
         // outside the moderate range, NaN / inf) is redone with the guarded M::observe — same bits either way.
         // (rows per block: four, two where the ring already holds 96 registers — PMSM's six leaves on the step-semantics path —
         // so that nothing spills)
-        constexpr int GW = (NR * W * (int)sizeof(T) / 4 >= 96) ? 2 : EXCENV_EMR_DEFER_ROWS;
+        constexpr int GW = (NR * W * (int)sizeof(T) / 4 >= 96) ? 2 : 4;
         constexpr int G = RPO < GW ? RPO : GW;
 #pragma unroll
         for (int t0 = 0; t0 < RPO; t0 += G) {
@@ -321,15 +291,9 @@ __global__ void __launch_bounds__(EM_LANES) __attribute__((amdgpu_waves_per_eu(2
 #pragma unroll
           for (int g = 0; g < G; ++g) put_row(t0 + g, obv[g]);
         }
-      } else if constexpr (NR <= 2 || EXCENV_EMR_ROW_UNROLL >= RPO) {  // the rows of a line as straight-line code
+      } else if constexpr (NR <= 2 || RPO == 1) {  // the rows of a line as straight-line code
 #pragma unroll
         for (int t = 0; t < RPO; ++t) row(t);
-      } else if constexpr (EXCENV_EMR_ROW_UNROLL == 2 && RPO % 2 == 0) {  // two rows' chains interleaved by the scheduler
-#pragma unroll 1
-        for (int t = 0; t < RPO; t += 2) {
-          row(t);
-          row(t + 1);
-        }
       } else {  // one row at a time: interleaved chains cost registers the ring needs
 #pragma unroll 1
         for (int t = 0; t < RPO; ++t) row(t);
@@ -352,7 +316,7 @@ __global__ void __launch_bounds__(EM_LANES) __attribute__((amdgpu_waves_per_eu(2
     // previous step, behind that step's flush and in front of its integration: nothing younger is in flight, so waiting for
     // everything outstanding waits for exactly that fill (and for older stores, which retire before it anyway).
     const int k1 = (n + 1 < N) ? n + 1 : N - 1;
-    if (!(EXCENV_EMR_DEBUG & 1) && k1 % ARW == 0 && k1 / ARW == w_hi && w_hi > 0) asm volatile("s_waitcnt vmcnt(0) expcnt(6)" ::: "memory");  // expcnt(6): never blocks, marks the hand-written wait (tools/isa_guards.py)
+    if (k1 % ARW == 0 && k1 / ARW == w_hi && w_hi > 0) asm volatile("s_waitcnt vmcnt(0) expcnt(6)" ::: "memory");  // expcnt(6): never blocks, marks the hand-written wait (tools/isa_guards.py)
     T a_nxt[A];  // requested here, used by the integration below: the save in between covers the LDS latency
     read_row(k1, a_nxt);
 #pragma unroll
@@ -374,13 +338,13 @@ __global__ void __launch_bounds__(EM_LANES) __attribute__((amdgpu_waves_per_eu(2
       if (j == CL || j == DL) continue;
       ring[ridx(j)][slot] = sv[j];
     }
-    if (!(EXCENV_EMR_DEBUG & 2) && (slot == W - 1 || n == N)) {
+    if (slot == W - 1 || n == N) {
       const int back = (n < slot) ? n : slot;  // rows of the window before row n
       flush(slot - back, slot, n - slot);
     }
     // row k1 was the last of its action window: the window's LDS is dead (its reads have returned by now; made formal) and
     // takes the next one — behind the flush, so that the wait at the top of the next step does not drain this step's stores
-    if (!(EXCENV_EMR_DEBUG & 1) && n < N && k1 % ARW == ARW - 1 && k1 / ARW == w_hi && (w_hi + 1) * ANP < n_pieces) {
+    if (n < N && k1 % ARW == ARW - 1 && k1 / ARW == w_hi && (w_hi + 1) * ANP < n_pieces) {
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       ++w_hi;
       dma_window(w_hi);

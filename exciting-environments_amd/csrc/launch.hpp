@@ -4,13 +4,14 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <type_traits>
 #include "kernels_emr.hpp"
 #include "refgen.hpp"
 
 namespace excenv {
 
 void set_error(const char* fmt, ...);
-// Set by EXCENV_LAUNCH_DYN when raising a kernel's dynamic-LDS limit failed (the launch is then skipped and
+// Set by launch_dyn when raising a kernel's dynamic-LDS limit failed (the launch is then skipped and
 // check_launch reports the stored message instead of a generic launch error). Per thread, like the error string.
 static thread_local bool g_attr_failed = false;
 // Which form of the trajectory kernel the last excenv_sim_ahead[_ws] call of this thread enqueued (excenv_last_launch(): tests
@@ -159,21 +160,27 @@ static bool fill_props(KProps<T, M>& kp, const excenv_props_t* p) {
 }
 
 // Launch with dynamic LDS; above the default 64 KiB limit the kernel's attribute is raised first (gfx950: 160 KiB per CU).
-#define EXCENV_LAUNCH_DYN(KERNEL, GRID, BLOCK, LDS, STREAM, ...)                                                         \
-  do {                                                                                                                   \
-    bool excenv_attr_ok = true;                                                                                          \
-    if ((LDS) > 64 * 1024) {                                                                                             \
-      const hipError_t excenv_e = hipFuncSetAttribute(reinterpret_cast<const void*>(&KERNEL),                            \
-                                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LDS));            \
-      if (excenv_e != hipSuccess) {                                                                                      \
-        set_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize = %d) failed: %s", (int)(LDS),                         \
-                  hipGetErrorString(excenv_e));                                                                          \
-        g_attr_failed = true;                                                                                            \
-        excenv_attr_ok = false;                                                                                          \
-      }                                                                                                                  \
-    }                                                                                                                    \
-    if (excenv_attr_ok) hipLaunchKernelGGL(KERNEL, GRID, BLOCK, LDS, STREAM, __VA_ARGS__);                               \
-  } while (0)
+template <typename... P, typename... A>
+static void launch_dyn(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t stream, const A&... args) {
+  if (lds > 64 * 1024) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) {
+      set_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize = %d) failed: %s", (int)lds, hipGetErrorString(e));
+      g_attr_failed = true;
+      return;
+    }
+  }
+  hipLaunchKernelGGL(kernel, grid, block, lds, stream, args...);
+}
+
+// A run-time value as a template argument: f(std::integral_constant<int, I>{}) for the I of the list that equals v. Returns what f
+// returns (whether it launched), false when no I matches.
+template <int... I, class F> static bool with_const(int v, F&& f) { return ((v == I && f(std::integral_constant<int, I>{})) || ...); }
+template <class F> static bool with_flag(bool b, F&& f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
+// The call's solver (check_common has validated the id)
+template <class F> static bool with_solver(int solver, F&& f) {
+  return with_const<EXCENV_EULER, EXCENV_RK4, EXCENV_TSIT5>(solver, static_cast<F&&>(f));
+}
 
 // Dynamic LDS for the saturated model's tables: staged when they fit LDS (<= 150 KiB, leaving room for one workgroup).
 // `other`: further dynamic LDS of the launch (returned with the tables' share); `static_bytes`: static LDS of the kernel itself
@@ -192,7 +199,7 @@ template <typename T, class M> static size_t lut_lds_bytes(KProps<T, M>& kp, siz
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 static inline int check_launch(const char* what) {
-  if (g_attr_failed) {  // message already set by EXCENV_LAUNCH_DYN
+  if (g_attr_failed) {  // message already set by launch_dyn
     g_attr_failed = false;
     (void)hipGetLastError();
     return EXCENV_EHIP;
@@ -281,123 +288,88 @@ template <class M, typename T> static int launch_step(const StepCall& sc) {
   constexpr int VWs = 16 / (int)sizeof(T);
   const bool dense = !general && V == 1 && (M::O % VWs) == 0 && (M::O / VWs) > 1;
   const size_t step_lds = lut_lds_bytes<T, M>(ka.kp, 0, dense ? sizeof(T) * BLOCK * M::O : 0);
-#define EXCENV_STEP_LAUNCH(SOLV, GEN, VV) EXCENV_LAUNCH_DYN((step_kernel<M, T, SOLV, GEN, VV>), grid, block, step_lds, sc.stream, ka)
-#define EXCENV_STEP_CASE(SOLV)                                                 \
-  case SOLV:                                                                   \
-    if (general) EXCENV_STEP_LAUNCH(SOLV, true, 1);                            \
-    else if (V == 2) EXCENV_STEP_LAUNCH(SOLV, false, 2);                       \
-    else if (V == 1) EXCENV_STEP_LAUNCH(SOLV, false, 1);                       \
-    else { if constexpr (sizeof(T) == 4) EXCENV_STEP_LAUNCH(SOLV, false, 4); } \
-    break;
-  switch (sc.solver) {
-    EXCENV_STEP_CASE(EXCENV_EULER)
-    EXCENV_STEP_CASE(EXCENV_RK4)
-    EXCENV_STEP_CASE(EXCENV_TSIT5)
-    default: set_error("bad solver id %d", sc.solver); return EXCENV_EINVAL;
-  }
-#undef EXCENV_STEP_CASE
-#undef EXCENV_STEP_LAUNCH
+  with_solver(sc.solver, [&](auto solver) {
+    constexpr int SOLVER = decltype(solver)::value;
+    if (general) launch_dyn(&step_kernel<M, T, SOLVER, true, 1>, grid, block, step_lds, sc.stream, ka);
+    else with_const<1, 2, 4>(V, [&](auto v) {
+      constexpr int VV = decltype(v)::value;
+      if constexpr (VV <= VMAX) launch_dyn(&step_kernel<M, T, SOLVER, false, VV>, grid, block, step_lds, sc.stream, ka);
+      return true;
+    });
+    return true;
+  });
   return check_launch("excenv_step");
 }
 
-// The lane-major trajectory kernel in the instantiation the plan names
-template <class M, typename T, int SOLVER, bool AHEAD>
-static void launch_sim_v(const SimPlan& p, SimArgs<T, M> ka, size_t lds_pad, hipStream_t stream) {
+// The trajectory kernels, one launcher per family. Each emits the instantiations sim_instantiated() (sim_plan.hpp) admits and no
+// other, and returns whether the plan named one of them. SEM: the semantics (the clock of the lane-major kernels).
+//
+// The lane-major kernel (kernels.hpp): sim_ahead_kernel, or sim_ahead_acc_t_kernel on the accumulated-time clock. The plan gives
+// the key (form, V, threads); STATES and LUT_LDS are the launch's own: general without / with the gym outputs' code (-2 / -1), lean
+// without / with state trajectories (0 / 1); look-up models one instantiation per place the tables live in (LDS when they fit,
+// lut_lds_bytes above).
+template <class M, typename T, int SOLVER, int SEM>
+static bool launch_lane_major(const SimPlan& p, SimArgs<T, M> ka, size_t lds_pad, T acc_step, T acc_end, hipStream_t stream) {
+  constexpr bool ACC_T = SEM == EXCENV_SEM_AHEAD_ACCUMULATED_T;
   const size_t lds = lut_lds_bytes<T, M>(ka.kp, lds_pad);
-  const int64_t lanes = ka.B / p.V;
-  const dim3 grid((unsigned)((lanes + p.threads - 1) / p.threads)), block(p.threads);
-  constexpr int VA = 16 / (int)sizeof(T);  // the widest form
-  // the widest forms: lean in 1024-thread workgroups (one barrier per row); lean with the gym outputs (LGYM: half of it, two
-  // environments per lane in fp32, was built and measured in round 4: PMSM 5.80 -> 7.26 ms, cart-pole 3.55 -> 4.34, acrobot 3.55 ->
-  // 4.11 — removed); row-major actions through the per-wave LDS piece ring (AEM)
-#define EXCENV_SIM_WIDEST(LDS, ...)                                                                                                     \
-  do {                                                                                                                                  \
-    if (ka.straj[0] == nullptr) EXCENV_LAUNCH_DYN((sim_ahead_kernel<M, T, SOLVER, AHEAD, false, VA, 0, __VA_ARGS__>), grid, block, LDS, stream, ka); \
-    else EXCENV_LAUNCH_DYN((sim_ahead_kernel<M, T, SOLVER, AHEAD, false, VA, 1, __VA_ARGS__>), grid, block, LDS, stream, ka);          \
-    return;                                                                                                                             \
-  } while (0)
-  constexpr int E = sizeof(T);
-  const bool wide = p.threads == WIDE_THREADS;
-  if constexpr (sim_wide_ok(M::ID, E, SOLVER, M::HAS_LUT)) if (p.form == SIM_LEAN && wide) EXCENV_SIM_WIDEST(lds, false, false, false, WIDE_THREADS);
-  if constexpr (sim_wide_gym_ok(M::ID, E, SOLVER, M::HAS_LUT)) if (p.form == SIM_LEAN_GYM && wide) EXCENV_SIM_WIDEST(lds, false, false, true, WIDE_THREADS);
-  if constexpr (!M::HAS_LUT) if (p.form == SIM_LEAN_GYM) EXCENV_SIM_WIDEST(lds, false, false, true);
-  if constexpr (!M::HAS_LUT && aem_fits(M::A, E)) if (p.form == SIM_AEM) { const size_t la = aem_lds_bytes<M, T, VA>() + lds; EXCENV_SIM_WIDEST(la, false, true); }
-#undef EXCENV_SIM_WIDEST
-  // look-up models: one instantiation per place the tables live in (LDS when they fit, lut_lds_bytes above)
-#define EXCENV_SIM_LAUNCH(GEN, VV, ST)                                                                                          \
-  do {                                                                                                                          \
-    if constexpr (M::HAS_LUT) {                                                                                                 \
-      if (ka.kp.lut_lds) {                                                                                                      \
-        EXCENV_LAUNCH_DYN((sim_ahead_kernel<M, T, SOLVER, AHEAD, GEN, VV, ST, true>), grid, block, lds, stream, ka);            \
-        return;                                                                                                                 \
-      }                                                                                                                         \
-    }                                                                                                                           \
-    EXCENV_LAUNCH_DYN((sim_ahead_kernel<M, T, SOLVER, AHEAD, GEN, VV, ST, false>), grid, block, lds, stream, ka);              \
-    return;                                                                                                                     \
-  } while (0)
-  if (p.form == SIM_GENERAL) {
-    if (ka.truncated == nullptr) EXCENV_SIM_LAUNCH(true, 1, -2);  // no gym trajectories: the instantiation without their code
-    EXCENV_SIM_LAUNCH(true, 1, -1);
-  }
-  if (ka.straj[0] == nullptr) {  // observations only: its own instantiations (no state stores between the action loads and their waits)
-    if constexpr (sizeof(T) == 4) {
-      if (p.V == 4) EXCENV_SIM_LAUNCH(false, 4, 0);
-    }
-    if (p.V == 2) EXCENV_SIM_LAUNCH(false, 2, 0);
-    EXCENV_SIM_LAUNCH(false, 1, 0);
-  }
-  if constexpr (sizeof(T) == 4) {
-    if (p.V == 4) EXCENV_SIM_LAUNCH(false, 4, 1);
-  }
-  if (p.V == 2) EXCENV_SIM_LAUNCH(false, 2, 1);
-  EXCENV_SIM_LAUNCH(false, 1, 1);
-#undef EXCENV_SIM_LAUNCH
+  return with_const<SIM_GENERAL, SIM_LEAN, SIM_LEAN_GYM, SIM_AEM>(p.form, [&](auto form) {
+    return with_const<1, 2, 4>(p.V, [&](auto v) {
+      return with_const<BLOCK, WIDE_THREADS>(p.threads, [&](auto nt) {
+        constexpr SimForm F = (SimForm)decltype(form)::value;
+        constexpr int V = decltype(v)::value, NT = decltype(nt)::value;
+        constexpr bool GEN = F == SIM_GENERAL;
+        if constexpr (!sim_instantiated(SimPlan{F, false, V, NT, 0, 0, false, 0, ACC_T}, SEM, M::ID, M::A, (int)sizeof(T), SOLVER,
+                                        M::HAS_LUT)) {
+          return false;
+        } else {
+          const dim3 grid((unsigned)((ka.B / V + NT - 1) / NT)), block(NT);
+          const size_t l = F == SIM_AEM ? aem_lds_bytes<M, T, V>() + lds : lds;  // AEM: the per-wave LDS piece ring of the actions
+          with_flag(GEN ? ka.truncated != nullptr : ka.straj[0] != nullptr, [&](auto st) {
+            return with_flag(ka.kp.lut_lds != 0, [&](auto lut_lds) {
+              constexpr int STATES = (GEN ? -2 : 0) + decltype(st)::value;
+              constexpr bool LUT_LDS = M::HAS_LUT && decltype(lut_lds)::value;
+              if constexpr (ACC_T)
+                launch_dyn(&sim_ahead_acc_t_kernel<M, T, SOLVER, GEN, V, STATES, LUT_LDS, NT>, grid, block, l, stream, ka, acc_step, acc_end);
+              else
+                launch_dyn(&sim_ahead_kernel<M, T, SOLVER, SEM == EXCENV_SEM_AHEAD, GEN, V, STATES, LUT_LDS, F == SIM_AEM, F == SIM_LEAN_GYM, NT>,
+                           grid, block, l, stream, ka);
+              return true;
+            });
+          });
+          return true;
+        }
+      });
+    });
+  });
 }
 
-// EXCENV_SEM_AHEAD_ACCUMULATED_T: the forms sim_plan.hpp can pick for it — general (with / without the gym outputs' code), lean
-// V = 1 / 2 / 4 with and without state trajectories, the look-up model's LDS-table variants, the 1024-thread lean form where
-// sim_wide_ok. Never the row-major action windows, the lean gym outputs or the env-major kernels (launch_sim checks).
-template <class M, typename T, int SOLVER>
-static void launch_sim_acc_t(const SimPlan& p, SimArgs<T, M> ka, T acc_step, T acc_end, size_t lds_pad, hipStream_t stream) {
-  const size_t lds = lut_lds_bytes<T, M>(ka.kp, lds_pad);
-  const int64_t lanes = ka.B / p.V;
-  const dim3 grid((unsigned)((lanes + p.threads - 1) / p.threads)), block(p.threads);
-  constexpr int VA = 16 / (int)sizeof(T);
-  if constexpr (sim_wide_ok(M::ID, (int)sizeof(T), SOLVER, M::HAS_LUT)) {
-    if (p.form == SIM_LEAN && p.threads == WIDE_THREADS) {
-      if (ka.straj[0] == nullptr) EXCENV_LAUNCH_DYN((sim_ahead_acc_t_kernel<M, T, SOLVER, false, VA, 0, false, WIDE_THREADS>), grid, block, lds, stream, ka, acc_step, acc_end);
-      else EXCENV_LAUNCH_DYN((sim_ahead_acc_t_kernel<M, T, SOLVER, false, VA, 1, false, WIDE_THREADS>), grid, block, lds, stream, ka, acc_step, acc_end);
-      return;
-    }
+// The LDS-ring env-major kernel (kernels_em.hpp): one wave per 64 environments, TK steps staged in LDS, per-env contiguous runs
+template <class M, typename T, int SOLVER, int SEM>
+static bool launch_em(const SimPlan& p, const SimArgs<T, M>& ka, hipStream_t stream) {
+  if constexpr (!sim_instantiated(SimPlan{SIM_EM, false, 1, EM_LANES, 0, 0, false, 0}, SEM, M::ID, M::A, (int)sizeof(T), SOLVER, M::HAS_LUT)) {
+    return false;
+  } else {
+    const size_t lds = em_lds_elems((int)sizeof(T), M::S, M::O) * sizeof(T);
+    const dim3 grid((unsigned)((ka.B + EM_LANES - 1) / EM_LANES)), block(EM_LANES);
+    return with_flag(p.form == SIM_EM_GENERAL, [&](auto general) {
+      launch_dyn(&sim_ahead_em_kernel<M, T, SOLVER, SEM == EXCENV_SEM_AHEAD, decltype(general)::value>, grid, block, lds, stream, ka);
+      return true;
+    });
   }
-#define EXCENV_ACC_LAUNCH(GEN, VV, ST)                                                                                        \
-  do {                                                                                                                        \
-    if constexpr (M::HAS_LUT) {                                                                                               \
-      if (ka.kp.lut_lds) {                                                                                                    \
-        EXCENV_LAUNCH_DYN((sim_ahead_acc_t_kernel<M, T, SOLVER, GEN, VV, ST, true>), grid, block, lds, stream, ka, acc_step, acc_end);           \
-        return;                                                                                                               \
-      }                                                                                                                       \
-    }                                                                                                                         \
-    EXCENV_LAUNCH_DYN((sim_ahead_acc_t_kernel<M, T, SOLVER, GEN, VV, ST, false>), grid, block, lds, stream, ka, acc_step, acc_end);             \
-    return;                                                                                                                   \
-  } while (0)
-  if (p.form == SIM_GENERAL) {
-    if (ka.truncated == nullptr) EXCENV_ACC_LAUNCH(true, 1, -2);
-    EXCENV_ACC_LAUNCH(true, 1, -1);
+}
+
+// The register-ring env-major kernel (kernels_emr.hpp): whole-line stores, lanes p.period environments apart (ka.a_wg)
+template <class M, typename T, int SOLVER, int SEM>
+static bool launch_emr(const SimPlan& p, const SimArgs<T, M>& ka, hipStream_t stream) {
+  if constexpr (!sim_instantiated(SimPlan{SIM_EMR, false, 1, EM_LANES, 0, 0, false, 0}, SEM, M::ID, M::A, (int)sizeof(T), SOLVER, M::HAS_LUT)) {
+    return false;
+  } else {
+    constexpr bool AHEAD = SEM == EXCENV_SEM_AHEAD;
+    const int64_t per = EM_LANES * p.period;
+    const dim3 grid((unsigned)(((ka.B + per - 1) / per) * p.period)), block(EM_LANES);
+    launch_dyn(&sim_ahead_emr_kernel<M, T, SOLVER, AHEAD>, grid, block, emr_lds_bytes<M, T, AHEAD>(), stream, ka);
+    return true;
   }
-  if (ka.straj[0] == nullptr) {
-    if constexpr (sizeof(T) == 4) {
-      if (p.V == 4) EXCENV_ACC_LAUNCH(false, 4, 0);
-    }
-    if (p.V == 2) EXCENV_ACC_LAUNCH(false, 2, 0);
-    EXCENV_ACC_LAUNCH(false, 1, 0);
-  }
-  if constexpr (sizeof(T) == 4) {
-    if (p.V == 4) EXCENV_ACC_LAUNCH(false, 4, 1);
-  }
-  if (p.V == 2) EXCENV_ACC_LAUNCH(false, 2, 1);
-  EXCENV_ACC_LAUNCH(false, 1, 1);
-#undef EXCENV_ACC_LAUNCH
 }
 
 // Validates the call, packs SimArgs and launches the form sc.plan names
@@ -406,7 +378,6 @@ template <class M, typename T> static int launch_sim(const SimCall& sc) {
   std::memset(&ka, 0, sizeof(ka));
   fill_props<T, M>(ka.kp, sc.props);
   double coef;
-  const bool acc_t = sc.semantics == EXCENV_SEM_AHEAD_ACCUMULATED_T;  // AHEAD-structured like EXCENV_SEM_AHEAD
   if (int rc = pmsm_coef<M>(sc.props, sc.env_tau, &coef, sc.semantics != EXCENV_SEM_STEP)) return rc;
   if (M::IS_PMSM && sc.substeps != 1) {
     set_error("PMSM: obs_stepsize must equal action_stepsize (reference pmsm_env.py:787)");
@@ -484,57 +455,11 @@ template <class M, typename T> static int launch_sim(const SimCall& sc) {
   }
 
   const SimPlan& p = sc.plan;
-  if (acc_t && (!p.acc_t || p.form == SIM_EMR || p.form == SIM_EM || p.form == SIM_EM_GENERAL || p.form == SIM_AEM ||
-                p.form == SIM_LEAN_GYM)) {  // sim_plan.hpp never plans these for it: the kernels have no accumulated-time form
-    set_error("excenv_sim_ahead: internal error: plan '%s' for EXCENV_SEM_AHEAD_ACCUMULATED_T", plan_name(p));
-    return EXCENV_EINVAL;
-  }
-  if constexpr (emr_supported(M::HAS_LUT)) {
-    if (p.form == SIM_EMR) {  // register-ring form (kernels_emr.hpp): whole-line stores, lanes p.period environments apart
-      SimArgs<T, M> kr = ka;
-      kr.a_wg = p.period;
-      const size_t emr_lds = sc.semantics == EXCENV_SEM_AHEAD ? emr_lds_bytes<M, T, true>() : emr_lds_bytes<M, T, false>();
-      const int64_t per = EM_LANES * p.period;
-      const dim3 grid((unsigned)(((sc.B + per - 1) / per) * p.period)), block(EM_LANES);
-#define EXCENV_EMR_CASE(SOLV)                                                                                                 \
-  case SOLV:                                                                                                                  \
-    if (sc.semantics == EXCENV_SEM_AHEAD) EXCENV_LAUNCH_DYN((sim_ahead_emr_kernel<M, T, SOLV, true>), grid, block, emr_lds, sc.stream, kr); \
-    else EXCENV_LAUNCH_DYN((sim_ahead_emr_kernel<M, T, SOLV, false>), grid, block, emr_lds, sc.stream, kr);             \
-    break;
-      switch (sc.solver) {
-        EXCENV_EMR_CASE(EXCENV_EULER)
-        EXCENV_EMR_CASE(EXCENV_RK4)
-        EXCENV_EMR_CASE(EXCENV_TSIT5)
-        default: set_error("bad solver id %d", sc.solver); return EXCENV_EINVAL;
-      }
-#undef EXCENV_EMR_CASE
-      g_last_launch = plan_name(p);
-      return check_launch("excenv_sim_ahead (env-major fused, register ring)");
-    }
-  }
-  if (p.form == SIM_EM || p.form == SIM_EM_GENERAL) {  // fused env-major kernel, one wave per 64 envs, TK steps staged in LDS,
-                                                       // per-env contiguous runs written out
-    const size_t lds = em_lds_elems((int)sizeof(T), M::S, M::O) * sizeof(T);
-    const dim3 grid((unsigned)((sc.B + EM_LANES - 1) / EM_LANES)), block(EM_LANES);
-#define EXCENV_EM_LAUNCH(SOLV, AH)                                                                                       \
-  if (general) EXCENV_LAUNCH_DYN((sim_ahead_em_kernel<M, T, SOLV, AH, true>), grid, block, lds, sc.stream, ka);         \
-  else EXCENV_LAUNCH_DYN((sim_ahead_em_kernel<M, T, SOLV, AH, false>), grid, block, lds, sc.stream, ka)
-#define EXCENV_EM_CASE(SOLV) \
-  case SOLV: if (sc.semantics == EXCENV_SEM_AHEAD) { EXCENV_EM_LAUNCH(SOLV, true); } else { EXCENV_EM_LAUNCH(SOLV, false); } break;
-    const bool general = p.form == SIM_EM_GENERAL;
-    switch (sc.solver) {
-      EXCENV_EM_CASE(EXCENV_EULER)
-      EXCENV_EM_CASE(EXCENV_RK4)
-      EXCENV_EM_CASE(EXCENV_TSIT5)
-      default: set_error("bad solver id %d", sc.solver); return EXCENV_EINVAL;
-    }
-#undef EXCENV_EM_CASE
-#undef EXCENV_EM_LAUNCH
-    g_last_launch = plan_name(p);
-    return check_launch("excenv_sim_ahead (env-major fused)");
-  }
-  ka.row_sync = p.row_sync;
-  {  // element offset of workgroup w's first env in each stream
+  const bool emr = p.form == SIM_EMR, env_major = emr || p.form == SIM_EM || p.form == SIM_EM_GENERAL;
+  if (emr) ka.a_wg = p.period;
+  if (!env_major) {
+    ka.row_sync = p.row_sync;
+    // element offset of workgroup w's first env in each stream
     const int64_t wg_envs = (int64_t)p.threads * p.V;
     auto wg_off = [&](int layout, int64_t sb, int64_t per_tile) -> int64_t {
       if (layout == EXCENV_LAYOUT_TILED) return (wg_envs == TILE) ? per_tile : -1;
@@ -551,21 +476,22 @@ template <class M, typename T> static int launch_sim(const SimCall& sc) {
   const size_t lds_pad = (size_t)sc.lds_pad + p.row_lds;
   // the accumulated-time clock's action step and end time, folded in double as oracle_body.inc does
   const T acc_step = (T)(sc.obs_stepsize * (double)sc.substeps), acc_end = (T)((sc.obs_stepsize * (double)sc.substeps) * (double)sc.K);
-#define EXCENV_SIM_CASE(SOLV)                                                                \
-  case SOLV:                                                                                 \
-    if (acc_t) launch_sim_acc_t<M, T, SOLV>(p, ka, acc_step, acc_end, lds_pad, sc.stream);   \
-    else if (sc.semantics == EXCENV_SEM_AHEAD) launch_sim_v<M, T, SOLV, true>(p, ka, lds_pad, sc.stream); \
-    else launch_sim_v<M, T, SOLV, false>(p, ka, lds_pad, sc.stream);                         \
-    break;
-  switch (sc.solver) {
-    EXCENV_SIM_CASE(EXCENV_EULER)
-    EXCENV_SIM_CASE(EXCENV_RK4)
-    EXCENV_SIM_CASE(EXCENV_TSIT5)
-    default: set_error("bad solver id %d", sc.solver); return EXCENV_EINVAL;
+  auto launch = [&](auto solver, auto sem) {
+    constexpr int SOLVER = decltype(solver)::value, SEM = decltype(sem)::value;
+    if (emr) return launch_emr<M, T, SOLVER, SEM>(p, ka, sc.stream);
+    if (env_major) return launch_em<M, T, SOLVER, SEM>(p, ka, sc.stream);
+    return launch_lane_major<M, T, SOLVER, SEM>(p, ka, lds_pad, acc_step, acc_end, sc.stream);
+  };
+  if (!sim_instantiated(p, sc.semantics, M::ID, M::A, (int)sizeof(T), sc.solver, M::HAS_LUT) || !with_solver(sc.solver, [&](auto solver) {
+        return with_const<EXCENV_SEM_STEP, EXCENV_SEM_AHEAD, EXCENV_SEM_AHEAD_ACCUMULATED_T>(sc.semantics, [&](auto sem) { return launch(solver, sem); });
+      })) {
+    set_error("excenv_sim_ahead: no kernel instantiation for plan '%s' (semantics %d, %d-byte elements)", plan_name(p), sc.semantics,
+              (int)sizeof(T));
+    return EXCENV_EINVAL;
   }
-#undef EXCENV_SIM_CASE
   g_last_launch = plan_name(p);
-  if (int rc = check_launch("excenv_sim_ahead")) return rc;
+  if (int rc = check_launch(emr ? "excenv_sim_ahead (env-major fused, register ring)" : env_major ? "excenv_sim_ahead (env-major fused)" : "excenv_sim_ahead"))
+    return rc;
   if (p.split_control) {
     ControlFillArgs<T, M> fa;
     std::memset(&fa, 0, sizeof(fa));

@@ -140,17 +140,6 @@ template <typename T> struct CartPole {
   }
 };
 
-// EXCENV_ACROBOT_ANGLE_SUM = 1 (build option, fp32 only, OFF by default): cos(theta_1 + pi/2) and cos(theta_1 + theta_2 + pi/2)
-// through -sin(theta_1) and -(sin theta_1 cos theta_2 + cos theta_1 sin theta_2) — one more sincos instead of two cos_t. Measured in
-// round 5 (same-session A/B, B = 2^22): acrobot Tsit5 8.97 -> 8.50 ms (0.211 -> 0.2225 of the HBM roof, +5.4 %), acrobot Euler flat.
-// Against the literal forms: identical for the first 10 rows of the reference's fixture, 1.2e-7 (full scale) at row 64, 3.6e-4 at
-// row 10 000 (both forms sit 1.5e-3 ... 1.9e-3 from the fp64 fixture there: the double pendulum's own amplification). It stays off
-// because the reference's expression rounds theta + pi/2 FIRST: at unwrapped angles of 1e4 ... 3e5 (sim_ahead integrates the raw
-// angle) that rounding is up to 0.015 rad, the identity does not reproduce it, and the oracle comparison at such angles
-// (test_unwrapped_angles_far_outside_the_principal_range) leaves its tolerance (2.1e-4 against 2e-4). Parity before 5 %.
-#ifndef EXCENV_ACROBOT_ANGLE_SUM
-#define EXCENV_ACROBOT_ANGLE_SUM 0
-#endif
 // ---- Acrobot: acrobot_env.py:171-197,247-248 ; P = (g,l_1,l_2,m_1,m_2,l_c1,l_c2,I_1,I_2) ----
 template <typename T> struct Acrobot {
   static constexpr int ID = EXCENV_ACROBOT, S = 4, A = 1, O = 4, P = 9, NY = 4, ND = 0;
@@ -176,19 +165,10 @@ template <typename T> struct Acrobot {
     const T d_22 = m_2 * (l_c2 * l_c2) + I_2;
     const T h_1 = -m_2 * l_1 * l_c2 * s2 * (omega_2 * omega_2) - T(2) * m_2 * l_1 * l_c2 * s2 * omega_1 * omega_2;
     const T h_2 = m_2 * l_1 * l_c2 * s2 * (omega_1 * omega_1);
-    T cA, cB;
-    if constexpr (EXCENV_ACROBOT_ANGLE_SUM != 0 && sizeof(T) == 4) {
-      // cos(x + pi/2) = -sin x and cos(x + y + pi/2) = -(sin x cos y + cos x sin y): ONE more sincos instead of two cos_t, whose
-      // argument sums each round first (the reference's expression, acrobot_env.py:182-183, kept literally in fp64 and in the
-      // oracle). Deviates from the literal form by the rounding of theta + pi/2 (~1e-7 in the argument): DESIGN.md §6.2b.
-      T s1, c1;
-      sincos_t(theta_1, s1, c1);
-      cA = -s1;
-      cB = -(s1 * c2 + c1 * s2);
-    } else {
-      cA = cos_t(theta_1 + K<T>::half_pi);
-      cB = cos_t(theta_1 + theta_2 + K<T>::half_pi);
-    }
+    // the reference's expressions literally (acrobot_env.py:182-183): theta + pi/2 rounds first. The angle-sum identities are 5 %
+    // faster for Tsit5 fp32 but do not reproduce that rounding at unwrapped angles
+    const T cA = cos_t(theta_1 + K<T>::half_pi);
+    const T cB = cos_t(theta_1 + theta_2 + K<T>::half_pi);
     const T phi_1 = (m_1 * l_c1 + m_2 * l_1) * g * cA + m_2 * l_c2 * g * cB;
     const T phi_2 = m_2 * l_c2 * g * cB;
     const T d_omega_1 = T(1) / (d_12 - d_22 / d_12 * d_11) * (u[0] + d_22 / d_12 * (h_1 + phi_1) - h_2 - phi_2);

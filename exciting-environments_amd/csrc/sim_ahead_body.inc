@@ -33,7 +33,7 @@
   Ctx<T, M>& c = cs[0];  // what is the same for every environment of the lane (dead time, look-up tables: V == 1 there)
 #define EXCENV_CX(v) cs[GENERAL ? (v) : 0]
   stage_lut<M, T>(c, ka.kp);
-  if constexpr (M::HAS_LUT) c.lut_lds = LUT_LDS ? 1 : 0;  // == ka.kp.lut_lds (launch_sim_v picks the instantiation by it)
+  if constexpr (M::HAS_LUT) c.lut_lds = LUT_LDS ? 1 : 0;  // == ka.kp.lut_lds (launch_lane_major picks the instantiation by it)
   // host guarantees B % V == 0; AEM: B % (64 V) == 0 — a wave is whole or absent (its lanes also fetch for each other)
   if (i0 >= ka.B) return;
 
@@ -573,8 +573,10 @@
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     fill_pending = false;
   }
-  // look-up models keep the single-step loop: twice the (large) look-up code does not fit the instruction cache
-  constexpr bool PINGPONG = !M::HAS_LUT && ((SOLVER == EXCENV_EULER) ? (EXCENV_PINGPONG & 1) : (EXCENV_PINGPONG & 2)) != 0;
+  // Euler: the K loop unrolled by two with ping-pong action registers (2-step prefetch distance, 2x loop code). Measured (DESIGN.md
+  // §6): +3.5 % Euler, -5 % Tsit5. Look-up models keep the single-step loop: twice the (large) look-up code does not fit the
+  // instruction cache
+  constexpr bool PINGPONG = SOLVER == EXCENV_EULER && !M::HAS_LUT;
   if constexpr (PINGPONG) {
     for (int64_t n = 0;; n += 2) {
       // even step: a0 holds action row k; the row of step n + 1 goes to a1 (clamped: always a valid row, so the load is

@@ -6,25 +6,15 @@
 #include <cstdint>
 #include "../../include/excenv.h"
 
-#ifndef EXCENV_BLOCK
-#define EXCENV_BLOCK 256
-#endif
-#ifndef EXCENV_EM_TK
-#define EXCENV_EM_TK 8  // steps per flush window for 4-byte elements (8-byte: half): the LDS ring of TK saved states per environment
-                        // decides how many waves fit a CU: TK = 8 -> 26.5 KB per wave (PMSM), six waves per CU; TK = 16 -> 41 KB, three
-#endif
-#ifndef EXCENV_EMR_MAX_RING_REGS
-#define EXCENV_EMR_MAX_RING_REGS 128
-#endif
-#ifndef EXCENV_ROW_SYNC_MIN_BATCH
-#define EXCENV_ROW_SYNC_MIN_BATCH ((int64_t)1 << 17)
-#endif
-
 namespace excenv {
 
-constexpr int BLOCK = EXCENV_BLOCK;
+constexpr int BLOCK = 256;
 constexpr int EM_LANES = 64;  // one wave per workgroup (the env-major kernels)
-static_assert(EXCENV_TILE % EXCENV_BLOCK == 0, "a workgroup must not straddle tiles of the tiled layout");
+static_assert(EXCENV_TILE % BLOCK == 0, "a workgroup must not straddle tiles of the tiled layout");
+// steps per flush window of the LDS-ring kernel for 4-byte elements (8-byte: half): the LDS ring of TK saved states per environment
+// decides how many waves fit a CU: TK = 8 -> 26.5 KB per wave (PMSM), six waves per CU; TK = 16 -> 41 KB, three
+constexpr int EM_TK = 8;
+constexpr int EMR_MAX_RING_REGS = 128;  // register budget of the register ring's 128-byte windows (4-byte elements; emr_rows)
 
 // Environments per lane by batch size (small batches: one, the per-step dependent chain of a wave as short as possible). Two per
 // lane from one wave per SIMD on the chip (1024 SIMDs x 64 lanes), FOUR only from two waves per SIMD: at B = 2^18 four per lane leave one 256-thread workgroup per CU — round 4, same-buffers A/B and fresh processes:
@@ -37,7 +27,7 @@ constexpr int auto_envs_per_lane(int64_t B, int vmax) {
 // they beat what the call would fall back to (a transposition pass, the one-environment general kernel) from one wave per SIMD on.
 constexpr bool widest_form_pays(int64_t B, int vmax) { return (B / vmax) >= (int64_t)1024 * 64; }
 
-constexpr int64_t ROW_SYNC_MIN_BATCH = EXCENV_ROW_SYNC_MIN_BATCH;  // one environment per lane: rows stored together from this batch on
+constexpr int64_t ROW_SYNC_MIN_BATCH = (int64_t)1 << 17;  // one environment per lane: rows stored together from this batch on
 // Threads per workgroup of the plain lean trajectory kernel (kernels.hpp, NT): 1024 with one barrier per row for the Euler kernels of
 // the small models, BLOCK everywhere else — measured per workload (profiles/r04_pattern_sweep.md): pendulum Euler fp32 -10.6 %, fp64
 // -8 %, MSD Euler fp32 -7 %, fp64 -6 %, tank Euler fp32 -6 % (fp64 +3 %: not taken); RK4 / Tsit5 of the same models +3 ... +9 %,
@@ -57,7 +47,7 @@ constexpr bool sim_wide_gym_ok(int env, int elem, int solver, bool lut) {
 constexpr bool aem_fits(int A, int elem) { return (16 / elem) % A == 0; }
 // The LDS-ring env-major kernel (kernels_em.hpp): steps per flush window and LDS elements per wave — the per-lane action line
 // (128 bytes + one 16-byte pad), the ring of saved states, one round of observation rows
-constexpr int em_tk(int elem) { return elem == 4 ? EXCENV_EM_TK : EXCENV_EM_TK / 2; }
+constexpr int em_tk(int elem) { return elem == 4 ? EM_TK : EM_TK / 2; }
 constexpr size_t em_lds_elems(int elem, int S, int O) { return (size_t)EM_LANES * (128 / elem + 16 / elem + S * (em_tk(elem) + 1) + O); }
 // The register-ring env-major kernel (kernels_emr.hpp). Leaves that need no window: one that never changes along a trajectory —
 // PMSM's omega_el (pmsm_env.py:509-523: the ODE has no equation for it; sim_ahead keeps it constant, :785-791) — and one that is a
@@ -73,11 +63,11 @@ constexpr int emr_ring_leaves(int S, bool pmsm, bool ahead) {
 // Steps per window. Two waves must share a SIMD (one wave alone leaves the VALU half idle: 9.9 ms for the headline launch with
 // 128-byte windows at one wave per SIMD, 7.7 ms with 64-byte windows at two), so a lane has 256 registers and the windows of
 // all ring leaves must fit next to the integration's own: 128-byte runs (whole lines, 32 registers per leaf) while the ring
-// stays within EXCENV_EMR_MAX_RING_REGS, else 64-byte runs (half lines, written 4 lanes x 16 bytes). PMSM in fp64 (5 ... 6 leaves
+// stays within EMR_MAX_RING_REGS, else 64-byte runs (half lines, written 4 lanes x 16 bytes). PMSM in fp64 (5 ... 6 leaves
 // x 8 doubles next to a double-precision integration) fits since the torque leaf left the ring and the action line is loaded at
 // the crossing: two registers are spilled, reloaded only on the IEEE-division fallback path of the flush.
 constexpr int emr_rows(int S, bool pmsm, bool ahead, int elem) {  // a double-precision integration needs twice the registers itself
-  return (emr_ring_leaves(S, pmsm, ahead) * 32 <= EXCENV_EMR_MAX_RING_REGS / (elem / 4) ? 128 : 64) / elem;
+  return (emr_ring_leaves(S, pmsm, ahead) * 32 <= EMR_MAX_RING_REGS / (elem / 4) ? 128 : 64) / elem;
 }
 // Environments between consecutive lanes of a register-ring wave: the period in e of the window phase (e * (K + 1)) % W
 constexpr int64_t emr_period(int64_t K, int64_t W) {
@@ -121,6 +111,31 @@ struct SimPlan {
   int64_t period;      // SIM_EMR: environments between the lanes of a wave
   bool acc_t = false;  // EXCENV_SEM_AHEAD_ACCUMULATED_T: the accumulated-time instantiations of GENERAL / LEAN (kernels.hpp ACC_T)
 };
+// Whether launch.hpp instantiates the kernel a plan names, for a model (env id, A, look-up tables attached), element size and solver.
+// The launchers emit exactly these instantiations and report any other plan as an error; tests/test_sim_plan.py checks that
+// sim_plan() picks only these. The accumulated-time kernel has the GENERAL / LEAN forms only (one action row per step is what the
+// row-major action windows, the fused env-major kernels and the lean gym outputs assume).
+constexpr bool sim_instantiated(const SimPlan& p, int semantics, int env, int A, int elem, int solver, bool lut) {
+  const bool acc_t = semantics == EXCENV_SEM_AHEAD_ACCUMULATED_T;
+  if ((elem != 4 && elem != 8) || solver < 0 || solver >= EXCENV_NUM_SOLVERS || semantics < EXCENV_SEM_STEP ||
+      semantics > EXCENV_SEM_AHEAD_ACCUMULATED_T || p.acc_t != acc_t)
+    return false;
+  const int VA = 16 / elem;  // the widest lane
+  switch (p.form) {
+    case SIM_GENERAL: return p.V == 1 && p.threads == BLOCK;
+    case SIM_LEAN:
+      if (p.threads == WIDE_THREADS) return p.V == VA && sim_wide_ok(env, elem, solver, lut);
+      return p.threads == BLOCK && (p.V == 1 || p.V == 2 || (p.V == 4 && elem == 4));
+    case SIM_LEAN_GYM:  // widest lane only: two environments per lane in fp32, built and measured in round 4, lost (PMSM 5.80 ->
+                        // 7.26 ms, cart-pole 3.55 -> 4.34, acrobot 3.55 -> 4.11)
+      return !acc_t && !lut && p.V == VA && (p.threads == BLOCK || (p.threads == WIDE_THREADS && sim_wide_gym_ok(env, elem, solver, lut)));
+    case SIM_AEM: return !acc_t && !lut && aem_fits(A, elem) && p.V == VA && p.threads == BLOCK;
+    case SIM_EM:
+    case SIM_EM_GENERAL: return !acc_t && p.V == 1 && p.threads == EM_LANES;
+    case SIM_EMR: return !acc_t && emr_supported(lut) && p.V == 1 && p.threads == EM_LANES;
+  }
+  return false;
+}
 
 namespace plan_detail {
 constexpr int vmax(const SimFacts& f) { return 16 / f.elem; }
@@ -271,7 +286,6 @@ constexpr const char* plan_name(const SimPlan& p) {
   if (p.acc_t) {  // GENERAL / LEAN only (sim_plan)
     if (p.via_workspace) return "transposition workspace + sim_ahead_kernel (accumulated t)";
     if (p.form == SIM_GENERAL) return "sim_ahead_kernel (general, accumulated t)";
-    if (p.form != SIM_LEAN) return "sim_ahead_kernel (unsupported form, accumulated t)";
     if (p.V == 1) return "sim_ahead_kernel (V=1, accumulated t)";
     if (p.V == 2) return wide ? "sim_ahead_kernel (V=2, 1024 threads, accumulated t)" : "sim_ahead_kernel (V=2, accumulated t)";
     return wide ? "sim_ahead_kernel (V=4, 1024 threads, accumulated t)" : "sim_ahead_kernel (V=4, accumulated t)";

@@ -1,7 +1,8 @@
 """The trajectory kernel's form for a call (csrc/sim_plan.hpp), checked without a GPU: the planner header is compiled with the host
 C++ compiler next to a small driver that reads call facts and prints the plan. The table covers every form, each lane-width cap,
 row_sync 0 / 1 / 2, the workgroup widths, the tiled layout, the workspace path, the flag alignment of the lean gym form and the
-shapes behind the last_launch() assertions of the GPU suite."""
+shapes behind the last_launch() assertions of the GPU suite. Every plan it yields must be one launch.hpp instantiates
+(sim_instantiated), and a few plans it never yields must not be."""
 import os
 import shutil
 import subprocess
@@ -26,8 +27,9 @@ int main() {
     int i = 0;
 %s
     const excenv::SimPlan p = excenv::sim_plan(f);
-    std::printf("%%d %%d %%d %%d %%d %%d %%d %%lld|%%s\n", (int)p.form, (int)p.via_workspace, p.V, p.threads, p.row_sync, p.row_lds,
-                (int)p.split_control, (long long)p.period, excenv::plan_name(p));
+    const bool inst = excenv::sim_instantiated(p, f.semantics, f.env, f.A, f.elem, f.solver, f.lut);
+    std::printf("%%d %%d %%d %%d %%d %%d %%d %%lld %%d|%%s\n", (int)p.form, (int)p.via_workspace, p.V, p.threads, p.row_sync, p.row_lds,
+                (int)p.split_control, (long long)p.period, (int)inst, excenv::plan_name(p));
   }
 }
 """ % (len(FIELDS), len(FIELDS), "\n".join(f"    f.{n} = (decltype(f.{n}))v[i++];" for n in FIELDS))
@@ -181,10 +183,69 @@ def planner(tmp_path_factory):
 def test_plan(planner, case):
     name, _, (form, V, threads, row_sync, split, period, launch) = case
     nums, got_name = planner[name].split("|")
-    f, ws, v, t, rs, _lds, sp, p = map(int, nums.split())
+    f, ws, v, t, rs, _lds, sp, p, inst = map(int, nums.split())
     assert (f, v, t, rs, sp, p, got_name) == (form, V, threads, row_sync, int(split), period, launch)
     assert ws == (launch.startswith("transposition"))
+    assert inst == 1
 
 
 def test_every_form_is_covered():
     assert {c[2][0] for c in CASES} == {GENERAL, LEAN, LEAN_GYM, AEM, EM, EM_GENERAL, EMR}
+
+
+# sim_instantiated() for plans given directly: (id, plan (form, V, threads, acc_t), semantics, model, dtype, solver, lut, expected)
+INSTANTIATED = r"""
+#include <cstdio>
+#include "sim_plan.hpp"
+int main() {
+  int form, V, threads, acc_t, semantics, env, A, elem, solver, lut;
+  while (std::scanf("%d %d %d %d %d %d %d %d %d %d", &form, &V, &threads, &acc_t, &semantics, &env, &A, &elem, &solver, &lut) == 10) {
+    const excenv::SimPlan p{(excenv::SimForm)form, false, V, threads, 0, 0, false, 0, acc_t != 0};
+    std::printf("%d\n", (int)excenv::sim_instantiated(p, semantics, env, A, elem, solver, lut != 0));
+  }
+}
+"""
+SEM_STEP, SEM_AHEAD, SEM_ACC_T = 0, 1, 2
+PLANS = [
+    ("lean gym", (LEAN_GYM, 4, 256, 0), SEM_AHEAD, "pmsm", F32, "euler", 0, True),
+    ("lean gym with a look-up table", (LEAN_GYM, 4, 256, 0), SEM_AHEAD, "pmsm", F32, "euler", 1, False),
+    ("lean gym with accumulated time", (LEAN_GYM, 4, 256, 1), SEM_ACC_T, "pmsm", F32, "euler", 0, False),
+    ("row-major actions", (AEM, 4, 256, 0), SEM_AHEAD, "pendulum", F32, "euler", 0, True),
+    ("row-major actions with accumulated time", (AEM, 4, 256, 1), SEM_ACC_T, "pendulum", F32, "euler", 0, False),
+    ("row-major actions below the widest lane", (AEM, 2, 256, 0), SEM_AHEAD, "pmsm", F32, "euler", 0, False),
+    ("lean V=4 fp32", (LEAN, 4, 256, 0), SEM_STEP, "cartpole", F32, "rk4", 0, True),
+    ("lean V=4 fp64", (LEAN, 4, 256, 0), SEM_STEP, "cartpole", F64, "rk4", 0, False),
+    ("lean V=4 look-up", (LEAN, 4, 256, 0), SEM_AHEAD, "pmsm", F32, "euler", 1, True),
+    ("lean 1024 threads", (LEAN, 4, 1024, 0), SEM_AHEAD, "pendulum", F32, "euler", 0, True),
+    ("lean 1024 threads accumulated time", (LEAN, 4, 1024, 1), SEM_ACC_T, "pendulum", F32, "euler", 0, True),
+    ("lean 1024 threads, not sim_wide_ok", (LEAN, 4, 1024, 0), SEM_AHEAD, "pmsm", F32, "euler", 0, False),
+    ("lean 1024 threads, RK4", (LEAN, 4, 1024, 0), SEM_AHEAD, "pendulum", F32, "rk4", 0, False),
+    ("lean 1024 threads below the widest lane", (LEAN, 2, 1024, 0), SEM_AHEAD, "pendulum", F32, "euler", 0, False),
+    ("lean gym 1024 threads fp64 pendulum", (LEAN_GYM, 2, 1024, 0), SEM_AHEAD, "pendulum", F64, "euler", 0, False),
+    ("general V=2", (GENERAL, 2, 256, 0), SEM_AHEAD, "pendulum", F32, "euler", 0, False),
+    ("env-major LDS ring with accumulated time", (EM, 1, 64, 1), SEM_ACC_T, "pmsm", F32, "euler", 0, False),
+    ("register ring look-up", (EMR, 1, 64, 0), SEM_AHEAD, "pmsm", F32, "euler", 1, False),
+    ("accumulated-time plan under SEM_AHEAD", (LEAN, 1, 256, 1), SEM_AHEAD, "pendulum", F32, "euler", 0, False),
+]
+
+
+@pytest.fixture(scope="module")
+def instantiated(tmp_path_factory):
+    if CXX is None:
+        pytest.skip("no host C++ compiler")
+    d = tmp_path_factory.mktemp("sim_instantiated")
+    src, exe = d / "driver.cpp", d / "driver"
+    src.write_text(INSTANTIATED)
+    subprocess.run([CXX, "-std=c++17", "-O1", "-Wall", "-Werror", "-I", CSRC, str(src), "-o", str(exe)], check=True)
+    rows = []
+    for _, (form, V, threads, acc_t), sem, model, dtype, solver, lut, _ in PLANS:
+        env, _S, A, _O = MODELS[model]
+        rows.append(f"{form} {V} {threads} {acc_t} {sem} {env} {A} {dtype} {SOLVERS[solver]} {lut}")
+    out = subprocess.run([str(exe)], input="\n".join(rows) + "\n", capture_output=True, text=True, check=True).stdout.split()
+    assert len(out) == len(PLANS)
+    return dict(zip((c[0] for c in PLANS), out))
+
+
+@pytest.mark.parametrize("case", PLANS, ids=[c[0] for c in PLANS])
+def test_instantiated(instantiated, case):
+    assert instantiated[case[0]] == str(int(case[-1]))

@@ -1,11 +1,12 @@
 """The planner (csrc/sim_plan.hpp) for EXCENV_SEM_AHEAD_ACCUMULATED_T, checked without a GPU through the driver of
 tests/test_sim_plan.py: exactly what EXCENV_SEM_AHEAD gets, except that the forms which assume one action row per step (row-major
-action windows, fused env-major kernels) and the lean gym outputs are never chosen, and the launch name says which clock ran."""
+action windows, fused env-major kernels) and the lean gym outputs are never chosen, and the launch name says which clock ran. Under
+all three semantics, every plan of a wider sweep is one launch.hpp instantiates (sim_instantiated)."""
 import subprocess
 
 import pytest
 
-from test_sim_plan import CASES, CXX, CSRC, DRIVER, EM_L, F32, F64, FIELDS, LANE, TILED, facts
+from test_sim_plan import CASES, CXX, CSRC, DRIVER, EM_L, F32, F64, FIELDS, LANE, MODELS, TILED, facts
 
 SEM_STEP, SEM_AHEAD, SEM_ACC_T = 0, 1, 2
 GENERAL, LEAN, LEAN_GYM, AEM, EM, EM_GENERAL, EMR = range(7)
@@ -25,28 +26,65 @@ for model in ("pendulum", "mass_spring_damper", "cartpole", "acrobot", "fluid_ta
             SHAPES.append(facts(model, dtype, B=4096, K=64, per_env_props=1))
             SHAPES.append(facts(model, dtype, B=4096, K=64, n_control=1))
             SHAPES.append(facts(model, dtype, B=1 << 20, K=100, envs_per_lane=1))
+# sim_instantiated's sweep: the shapes above plus the facts that pick the look-up model, the general kernel, the control-column fill
+# and the lane width
+SWEEP = list(SHAPES)
+for model in MODELS:
+    for lut in ((0, 1) if model == "pmsm" else (0,)):
+        for dtype in (F32, F64):
+            for solver in ("euler", "rk4", "tsit5"):
+                for B in (2048, 1 << 22):
+                    for al, tl in ((LANE, LANE), (EM_L, LANE), (EM_L, EM_L), (TILED, TILED)):
+                        for gym in (0, 1):
+                            for pe in (0, 1):
+                                for nc in (0, 1):
+                                    for epl in (0, 1, 2, 4):
+                                        for ws in (0, 1):
+                                            SWEEP.append(facts(model, dtype, solver, B=B, K=64, action_layout=al, traj_layout=tl, gym=gym,
+                                                               lut=lut, per_env_props=pe, n_control=nc, envs_per_lane=epl, workspace=ws,
+                                                               workspace_bytes=(1 << 40) if ws else 0))
+
+
+def run_driver(tmp_path_factory, rows):
+    d = tmp_path_factory.mktemp("sim_plan_acc_t")
+    src, exe = d / "driver.cpp", d / "driver"
+    src.write_text(DRIVER)
+    subprocess.run([CXX, "-std=c++17", "-O1", "-Wall", "-Werror", "-I", CSRC, str(src), "-o", str(exe)], check=True)
+    out = subprocess.run([str(exe)], input="\n".join(rows) + "\n", capture_output=True, text=True, check=True).stdout.splitlines()
+    assert len(out) == len(rows)
+    return out
+
+
+def parse(line):
+    nums, name = line.split("|")
+    form, ws, V, threads, row_sync, _lds, split, _period, inst = map(int, nums.split())
+    return dict(form=form, ws=ws, V=V, threads=threads, row_sync=row_sync, split=split, inst=inst, name=name)
 
 
 @pytest.fixture(scope="module")
 def plans(tmp_path_factory):
     if CXX is None:
         pytest.skip("no host C++ compiler")
-    d = tmp_path_factory.mktemp("sim_plan_acc_t")
-    src, exe = d / "driver.cpp", d / "driver"
-    src.write_text(DRIVER)
-    subprocess.run([CXX, "-std=c++17", "-O1", "-Wall", "-Werror", "-I", CSRC, str(src), "-o", str(exe)], check=True)
     rows = []
     for f in SHAPES:
         for sem in (SEM_AHEAD, SEM_ACC_T):
             rows.append(" ".join(str(dict(f, semantics=sem)[n]) for n in FIELDS))
-    out = subprocess.run([str(exe)], input="\n".join(rows) + "\n", capture_output=True, text=True, check=True).stdout.splitlines()
-    assert len(out) == 2 * len(SHAPES)
-
-    def parse(line):
-        nums, name = line.split("|")
-        form, ws, V, threads, row_sync, _lds, split, _period = map(int, nums.split())
-        return dict(form=form, ws=ws, V=V, threads=threads, row_sync=row_sync, split=split, name=name)
+    out = run_driver(tmp_path_factory, rows)
     return [(f, parse(out[2 * i]), parse(out[2 * i + 1])) for i, f in enumerate(SHAPES)]
+
+
+def test_every_plan_is_instantiated(tmp_path_factory):
+    if CXX is None:
+        pytest.skip("no host C++ compiler")
+    sems = (SEM_STEP, SEM_AHEAD, SEM_ACC_T)
+    rows = [" ".join(str(dict(f, semantics=sem)[n]) for n in FIELDS) for f in SWEEP for sem in sems]
+    out = run_driver(tmp_path_factory, rows)
+    missing = [(SWEEP[i // len(sems)], sems[i % len(sems)], line) for i, line in enumerate(out) if not parse(line)["inst"]]
+    assert not missing, missing[:5]
+    # the sweep reaches every form, the look-up model's and the 1024-thread ones included
+    forms = {(parse(line)["form"], parse(line)["threads"]) for line in out}
+    assert {(GENERAL, 256), (LEAN, 256), (LEAN, 1024), (LEAN_GYM, 256), (LEAN_GYM, 1024), (AEM, 256), (EM, 64), (EM_GENERAL, 64),
+            (EMR, 64)} <= forms
 
 
 def test_never_a_form_without_an_accumulated_time_instantiation(plans):
