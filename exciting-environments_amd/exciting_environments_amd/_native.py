@@ -3,6 +3,11 @@
 This is the only compute backend of the package. There is no CPU or PyTorch fallback: if the
 shared library is missing, or no HIP device is present when a kernel entry point is called, the
 call raises.
+
+One convention for every entry point: `PROTOTYPES` gives each function of the header its restype and argtypes, so callers pass
+plain Python ints / floats / None, `byref()` results and pointer arrays (a bare int for a pointer argument is converted as a
+64-bit address, never truncated). The constants and structures below mirror the header; tests/test_native_binding.py compares
+them with it (values, sizes, field offsets, argument counts).
 """
 from __future__ import annotations
 
@@ -20,6 +25,7 @@ SEM_AHEAD_ACCUMULATED_T = 2  # opt-in: diffrax's accumulated-time clock as the C
 # CoreEnvironment.sim_ahead_semantics -> excenv_semantics_t
 SEMANTICS = {"step": SEM_STEP, "ahead": SEM_AHEAD, "ahead_accumulated_t": SEM_AHEAD_ACCUMULATED_T}
 F32, F64 = 0, 1
+OPT_NO_FUSED_ACTIONS = 1  # EXCENV_OPT_NO_FUSED_ACTIONS
 ABI_VERSION = 7
 
 _LIB_PATH = os.environ.get(  # EXCENV_HIP_LIB: A/B-test another build of the same library (tuning experiments)
@@ -68,6 +74,42 @@ class Control(ctypes.Structure):
     ]
 
 
+# the C types of the header's structures (tests/test_native_binding.py compares sizes and field offsets with the host compiler's)
+STRUCTS = {Param: "excenv_param_t", PmsmLut: "excenv_pmsm_lut_t", Props: "excenv_props_t", LaunchOpts: "excenv_launch_opts_t",
+           TrajGym: "excenv_traj_gym_t", Control: "excenv_control_t"}
+
+_vp, _ci, _i32, _i64, _cd = ctypes.c_void_p, ctypes.c_int, ctypes.c_int32, ctypes.c_int64, ctypes.c_double
+_STEP = [_ci, _ci, _ci, _i64, _vp, _vp, _cd, _vp, _vp, _vp, _vp]  # env, solver, dtype, B, props, control, tau, in, action, out, obs
+_AHEAD = [_ci, _ci, _ci, _i64, _i64, _i32, _vp, _vp, _cd, _cd, _vp, _vp, _ci, _vp, _vp, _ci, _vp, _ci, _vp]  # ... semantics, gym
+# every function include/excenv.h declares: (restype, argtypes). Every pointer is a void*: structures go in as byref(), arrays as
+# ctypes arrays, device addresses as plain ints.
+PROTOTYPES = {
+    "excenv_abi_version": (_ci, []),
+    "excenv_last_error": (ctypes.c_char_p, []),
+    "excenv_last_launch": (ctypes.c_char_p, []),
+    "excenv_env_dims": (_ci, [_ci, _vp, _vp, _vp, _vp]),
+    "excenv_step_bytes": (_i64, [_ci, _ci]),
+    "excenv_sim_ahead_bytes": (_i64, [_ci, _ci, _ci]),
+    "excenv_step": (_ci, _STEP + [_vp, _vp]),
+    "excenv_truncated_width": (_i32, [_ci, _i32]),
+    "excenv_gym_step": (_ci, _STEP + [_vp, _vp, _vp, _vp, _vp]),
+    "excenv_sim_ahead": (_ci, _AHEAD + [_vp, _vp]),
+    "excenv_sim_ahead_workspace_bytes": (_i64, [_ci, _ci, _i64, _i64, _i32, _i32, _ci, _ci, _ci]),
+    "excenv_sim_ahead_ws": (_ci, _AHEAD + [_vp, _i64, _vp, _vp]),
+    "excenv_sim_ahead_fuses_actions": (_ci, [_ci, _ci, _ci, _i64, _i64, _vp, _i32, _ci, _ci, _ci, _vp, _vp]),
+    "excenv_transpose": (_ci, [_ci, _i64, _i64, _vp, _vp, _vp]),
+    "excenv_rew_trunc_term": (_ci, [_ci, _ci, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _ci, _vp]),
+    "excenv_state_from_observation": (_ci, [_ci, _ci, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "excenv_update_ref": (_ci, [_ci, _ci, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
+    "excenv_observe": (_ci, [_ci, _ci, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "excenv_update_ref_to": (_ci, [_ci, _ci, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
+    "excenv_random_state": (_ci, [_ci, _ci, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "excenv_allgather": (_ci, [_vp, _ci, _vp, _vp, _i64, _vp]),
+    "excenv_stream_pattern": (_ci, [_i32, _vp, _vp, _i32, _vp, _vp, _i64, _i64, _i32, _vp]),
+    "excenv_probe_math": (_ci, [_ci, _ci, _i64, _vp, _vp, _vp]),
+    "excenv_probe_div": (_ci, [_ci, _i64, _vp, _vp, _vp, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -86,27 +128,9 @@ def lib():
                 "There is no CPU fallback."
             )
         l = ctypes.CDLL(_LIB_PATH)
-        l.excenv_last_error.restype = ctypes.c_char_p
-        l.excenv_last_launch.restype = ctypes.c_char_p
-        l.excenv_abi_version.restype = ctypes.c_int
-        l.excenv_step_bytes.restype = ctypes.c_int64
-        l.excenv_sim_ahead_bytes.restype = ctypes.c_int64
-        l.excenv_sim_ahead_workspace_bytes.restype = ctypes.c_int64
-        l.excenv_truncated_width.restype = ctypes.c_int32
-        for fn in ("excenv_step", "excenv_gym_step", "excenv_sim_ahead", "excenv_sim_ahead_ws", "excenv_transpose", "excenv_env_dims",
-                   "excenv_probe_math", "excenv_probe_div", "excenv_rew_trunc_term", "excenv_state_from_observation",
-                   "excenv_update_ref", "excenv_update_ref_to", "excenv_random_state", "excenv_observe", "excenv_stream_pattern",
-                   "excenv_allgather"):
-            getattr(l, fn).restype = ctypes.c_int
-        vp, ci, cl, cd = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_double
-        # typed prototypes: plain Python ints / floats / None / byref() pass without per-call ctypes wrapping
-        l.excenv_step.argtypes = [ci, ci, ci, cl, vp, vp, cd, vp, vp, vp, vp, vp, vp]
-        l.excenv_gym_step.argtypes = [ci, ci, ci, cl, vp, vp, cd, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-        l.excenv_sim_ahead_ws.argtypes = [ci, ci, ci, cl, cl, ctypes.c_int32, vp, vp, cd, cd, vp, vp, ci, vp, vp, ci, vp, ci, vp,
-                                          vp, cl, vp, vp]
-        l.excenv_stream_pattern.argtypes = [ctypes.c_int32, vp, vp, ctypes.c_int32, vp, vp, cl, cl, ctypes.c_int32, vp]
-        l.excenv_sim_ahead_fuses_actions.restype = ctypes.c_int
-        l.excenv_sim_ahead_fuses_actions.argtypes = [ci, ci, ci, cl, cl, vp, ctypes.c_int32, ci, ci, ci, vp, vp]
+        for name, (restype, argtypes) in PROTOTYPES.items():
+            fn = getattr(l, name)
+            fn.restype, fn.argtypes = restype, argtypes
         if l.excenv_abi_version() != ABI_VERSION:
             raise ImportError("libexcenv_hip.so: ABI version mismatch")
         _lib = l
@@ -117,19 +141,6 @@ def _check(rc: int, what: str):
     if rc != 0:
         msg = lib().excenv_last_error().decode("utf-8", "replace")
         raise RuntimeError(f"{what} failed (rc={rc}): {msg}")
-
-
-def allgather(nccl_comm: int, send: torch.Tensor, recv: torch.Tensor):
-    """excenv_allgather: ncclAllGather of `send` (this rank's contiguous slice) into `recv` ([world * send.numel()]) on torch's
-    current stream, through the caller's ncclComm_t handle (an integer address). The Python mirror's ObservationGatherer uses
-    torch.distributed instead; this is the entry point a non-torch binder would call."""
-    _require_device(send, "excenv_allgather")
-    assert send.is_contiguous() and recv.is_contiguous() and send.dtype == recv.dtype
-    with _on_device(send.device):
-        rc = lib().excenv_allgather(ctypes.c_void_p(nccl_comm), ctypes.c_int(dtype_id(send.dtype)), ctypes.c_void_p(send.data_ptr()),
-                                    ctypes.c_void_p(recv.data_ptr()), ctypes.c_int64(send.numel()),
-                                    ctypes.c_void_p(_raw_stream(send.device)))
-    _check(rc, "excenv_allgather")
 
 
 def last_launch() -> str:
@@ -152,12 +163,20 @@ def _require_device(t: torch.Tensor, what: str):
         )
 
 
+# private fast accessors of torch when this build has them, the public (slower) API otherwise
+_get_raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None) or (lambda i: torch.cuda.current_stream(i).cuda_stream)
+cuda_get_device = getattr(torch._C, "_cuda_getDevice", None) or torch.cuda.current_device
+cuda_is_capturing = getattr(torch._C, "_cuda_isCurrentStreamCapturing", None) or torch.cuda.is_current_stream_capturing
+
+
+def raw_stream(device_index: int) -> int:
+    """torch's current HIP stream on the device of that index as an integer handle (hipStream_t)."""
+    return _get_raw_stream(device_index)
+
+
 def _raw_stream(device: torch.device) -> int:
-    """hipStream_t of torch's current stream on `device` (the fast private accessor when torch has it)."""
-    try:
-        return torch._C._cuda_getCurrentRawStream(device.index if device.index is not None else torch.cuda.current_device())
-    except AttributeError:  # pragma: no cover
-        return torch.cuda.current_stream(device).cuda_stream
+    """raw_stream() of a torch.device (no index: the current device)."""
+    return _get_raw_stream(device.index if device.index is not None else cuda_get_device())
 
 
 class _on_device:
@@ -176,8 +195,17 @@ class _on_device:
             self.ctx.__exit__(*a)
 
 
-def _ptrs(tensors: Sequence[torch.Tensor]):
-    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+def _ref(struct):
+    """byref(struct), or NULL for None (optional excenv_control_t / excenv_launch_opts_t / excenv_traj_gym_t arguments)."""
+    return None if struct is None else ctypes.byref(struct)
+
+
+def _ptr(t: Optional[torch.Tensor]):
+    return None if t is None else t.data_ptr()
+
+
+def _ptrs(tensors: Optional[Sequence[torch.Tensor]]):
+    return None if tensors is None else (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
 
 
 def ptr_array(addresses: Sequence[int]):
@@ -185,12 +213,28 @@ def ptr_array(addresses: Sequence[int]):
     return (ctypes.c_void_p * len(addresses))(*addresses)
 
 
-_get_raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
+def _i32s(values: Sequence[int]):
+    return (ctypes.c_int32 * len(values))(*values) if values else None
 
 
-def raw_stream(device_index: int) -> int:
-    """The current HIP stream of the (current) device as an integer handle."""
-    return _get_raw_stream(device_index) if _get_raw_stream is not None else torch.cuda.current_stream().cuda_stream
+def _launch(name: str, on: torch.Tensor, what: str, *args):
+    """One launching entry point (the C arguments in front of `stream`) on the current stream of the device `on` lives on."""
+    _require_device(on, what)
+    fn = getattr(lib(), name)
+    with _on_device(on.device):
+        rc = fn(*args, _raw_stream(on.device))
+    if rc != 0:
+        _check(rc, name)
+
+
+def allgather(nccl_comm: int, send: torch.Tensor, recv: torch.Tensor):
+    """excenv_allgather: ncclAllGather of `send` (this rank's contiguous slice) into `recv` ([world * send.numel()]) on torch's
+    current stream, through the caller's ncclComm_t handle (an integer address). The Python mirror's ObservationGatherer uses
+    torch.distributed instead; this is the entry point a non-torch binder would call."""
+    _require_device(send, "excenv_allgather")
+    assert send.is_contiguous() and recv.is_contiguous() and send.dtype == recv.dtype
+    _launch("excenv_allgather", send, "excenv_allgather", nccl_comm, dtype_id(send.dtype), send.data_ptr(), recv.data_ptr(),
+            send.numel())
 
 
 def step_raw(env_id, solver_id, dtype_code, B, props_ref, control_ref, tau, in_ptrs, action_ptr, out_ptrs, obs_ptr, opts_ref,
@@ -206,6 +250,46 @@ def step_raw(env_id, solver_id, dtype_code, B, props_ref, control_ref, tau, in_p
                                   obs_ptr, gym[0], gym[1], gym[2], opts_ref, stream)
     if rc != 0:
         _check(rc, "excenv_step" if gym is None else "excenv_gym_step")
+
+
+def step(env_id, solver_id, dtype, B, props: Props, control: Optional[Control], tau: float,
+         state_in: Sequence[torch.Tensor], action: torch.Tensor, state_out: Sequence[torch.Tensor],
+         obs: torch.Tensor, opts: Optional[LaunchOpts] = None):
+    _require_device(action, "vmap_step")
+    lib()
+    with _on_device(action.device):
+        step_raw(env_id, solver_id, dtype_id(dtype), B, ctypes.byref(props), _ref(control), tau, _ptrs(state_in),
+                 action.data_ptr(), _ptrs(state_out), obs.data_ptr(), _ref(opts), _raw_stream(action.device))
+
+
+def sim_ahead_raw(env_id, solver_id, dtype_code, B, K, substeps, props_ref, control_ref, obs_stepsize, env_tau, in_ptrs,
+                  actions_ptr, action_layout, obs_ptr, traj_ptrs, traj_layout, last_ptrs, semantics, ws_ptr, ws_bytes, opts_ref,
+                  stream, gym_ref=None):
+    """excenv_sim_ahead_ws with every argument already in its C form (what vmap_sim_ahead calls; gym_ref: None or
+    byref(TrajGym)). The caller has made the buffers' device current."""
+    rc = _lib.excenv_sim_ahead_ws(env_id, solver_id, dtype_code, B, K, substeps, props_ref, control_ref, obs_stepsize, env_tau,
+                                  in_ptrs, actions_ptr, action_layout, obs_ptr, traj_ptrs, traj_layout, last_ptrs, semantics,
+                                  gym_ref, ws_ptr, ws_bytes, opts_ref, stream)
+    if rc != 0:
+        _check(rc, "excenv_sim_ahead")
+
+
+def sim_ahead(env_id, solver_id, dtype, B, K, substeps, props: Props, control: Optional[Control],
+              obs_stepsize: float, env_tau: float, state_in: Sequence[torch.Tensor], actions: torch.Tensor,
+              action_layout: int, obs_traj: torch.Tensor, state_traj: Optional[Sequence[torch.Tensor]],
+              traj_layout: int, last_state: Sequence[torch.Tensor], semantics: int,
+              workspace: Optional[torch.Tensor] = None, opts: Optional[LaunchOpts] = None, gym=None):
+    """sim_ahead_raw for tensors. gym: None or (reward, terminated, truncated) device tensors in the trajectory layout
+    (excenv_traj_gym_t)."""
+    _require_device(obs_traj, "vmap_sim_ahead")
+    g = None if gym is None else TrajGym(*[t.data_ptr() for t in gym])
+    lib()
+    with _on_device(obs_traj.device):
+        sim_ahead_raw(env_id, solver_id, dtype_id(dtype), B, K, substeps, ctypes.byref(props), _ref(control), obs_stepsize,
+                      env_tau, _ptrs(state_in), actions.data_ptr() if K > 0 else None, action_layout, obs_traj.data_ptr(),
+                      _ptrs(state_traj), traj_layout, _ptrs(last_state), semantics, _ptr(workspace),
+                      workspace.numel() * workspace.element_size() if workspace is not None else 0, _ref(opts),
+                      _raw_stream(obs_traj.device), _ref(g))
 
 
 def stream_pattern(read_ptrs, read_row_strides, write_ptrs, write_row_strides, row_bytes: int, rows: int, stream: int,
@@ -269,24 +353,25 @@ def raw_malloc(nbytes: int):
 def raw_free(ptr):
     h = _hip_runtime()
     if h is not None and ptr:
-        h.hipFree(ctypes.c_void_p(ptr))
+        h.hipFree(ptr)
 
 
 def env_dims(env_id: int):
-    S, A, O, P = (ctypes.c_int32() for _ in range(4))
-    _check(lib().excenv_env_dims(env_id, ctypes.byref(S), ctypes.byref(A), ctypes.byref(O), ctypes.byref(P)), "excenv_env_dims")
-    return S.value, A.value, O.value, P.value
+    dims = (ctypes.c_int32 * 4)()  # S, A, O, P
+    _check(lib().excenv_env_dims(env_id, *[ctypes.byref(dims, 4 * i) for i in range(4)]), "excenv_env_dims")
+    return tuple(dims)
 
 
 def step_bytes(env_id: int, dtype: torch.dtype) -> int:
-    return int(lib().excenv_step_bytes(env_id, dtype_id(dtype)))
+    return lib().excenv_step_bytes(env_id, dtype_id(dtype))
 
 
 def sim_ahead_bytes(env_id: int, dtype: torch.dtype, with_state_traj: bool = True) -> int:
-    return int(lib().excenv_sim_ahead_bytes(env_id, dtype_id(dtype), int(with_state_traj)))
+    return lib().excenv_sim_ahead_bytes(env_id, dtype_id(dtype), int(with_state_traj))
 
 
-OPT_NO_FUSED_ACTIONS = 1  # EXCENV_OPT_NO_FUSED_ACTIONS
+def truncated_width(env_id: int, n_control: int) -> int:
+    return lib().excenv_truncated_width(env_id, n_control)
 
 
 def launch_opts(envs_per_lane: int = 0, env_major_mode: int = 0, lds_pad_bytes: int = 0, flags: int = 0) -> LaunchOpts:
@@ -297,12 +382,13 @@ def sim_ahead_fuses_actions(env: int, solver: int, dtype: torch.dtype, B: int, K
                             action_layout: int, traj_layout: int, actions_ptr: int, opts: Optional[LaunchOpts]) -> bool:
     """excenv_sim_ahead_fuses_actions: the trajectory kernel reads these row-major actions itself (no workspace needed)."""
     return bool(lib().excenv_sim_ahead_fuses_actions(env, solver, dtype_id(dtype), B, K, ctypes.byref(props), n_control, int(with_gym),
-                                                     action_layout, traj_layout, actions_ptr,
-                                                     ctypes.byref(opts) if opts is not None else None))
+                                                     action_layout, traj_layout, actions_ptr, _ref(opts)))
 
 
-def _opts_ref(opts: Optional[LaunchOpts]):
-    return ctypes.byref(opts) if opts is not None else None
+def sim_ahead_workspace_bytes(env_id, dtype, B, K, substeps, n_control, action_layout, traj_layout,
+                              with_state_traj=True) -> int:
+    return lib().excenv_sim_ahead_workspace_bytes(env_id, dtype_id(dtype), B, K, substeps, n_control, action_layout, traj_layout,
+                                                  int(with_state_traj))
 
 
 def make_control(control_idx: Sequence[int], refs: Sequence[torch.Tensor],
@@ -319,108 +405,22 @@ def make_control(control_idx: Sequence[int], refs: Sequence[torch.Tensor],
     return c
 
 
-def step(env_id, solver_id, dtype, B, props: Props, control: Optional[Control], tau: float,
-         state_in: Sequence[torch.Tensor], action: torch.Tensor, state_out: Sequence[torch.Tensor],
-         obs: torch.Tensor, opts: Optional[LaunchOpts] = None):
-    _require_device(action, "vmap_step")
-    with _on_device(action.device):
-        stream = _raw_stream(action.device)
-        rc = lib().excenv_step(
-            ctypes.c_int(env_id), ctypes.c_int(solver_id), ctypes.c_int(dtype_id(dtype)), ctypes.c_int64(B),
-            ctypes.byref(props), ctypes.byref(control) if control is not None else None, ctypes.c_double(tau),
-            _ptrs(state_in), ctypes.c_void_p(action.data_ptr()), _ptrs(state_out), ctypes.c_void_p(obs.data_ptr()),
-            _opts_ref(opts), ctypes.c_void_p(stream),
-        )
-    _check(rc, "excenv_step")
-
-
-def truncated_width(env_id: int, n_control: int) -> int:
-    return int(lib().excenv_truncated_width(ctypes.c_int(env_id), ctypes.c_int32(n_control)))
-
-
-def gym_step(env_id, solver_id, dtype, B, props: Props, control: Optional[Control], tau: float,
-             state_in: Sequence[torch.Tensor], action: torch.Tensor, state_out: Sequence[torch.Tensor],
-             obs: torch.Tensor, reward: torch.Tensor, terminated: torch.Tensor, truncated: torch.Tensor,
-             opts: Optional[LaunchOpts] = None):
-    _require_device(action, "gym_step")
-    with _on_device(action.device):
-        stream = _raw_stream(action.device)
-        rc = lib().excenv_gym_step(
-            ctypes.c_int(env_id), ctypes.c_int(solver_id), ctypes.c_int(dtype_id(dtype)), ctypes.c_int64(B),
-            ctypes.byref(props), ctypes.byref(control) if control is not None else None, ctypes.c_double(tau),
-            _ptrs(state_in), ctypes.c_void_p(action.data_ptr()), _ptrs(state_out), ctypes.c_void_p(obs.data_ptr()),
-            ctypes.c_void_p(reward.data_ptr()), ctypes.c_void_p(terminated.data_ptr()),
-            ctypes.c_void_p(truncated.data_ptr()), _opts_ref(opts), ctypes.c_void_p(stream),
-        )
-    _check(rc, "excenv_gym_step")
-
-
-def sim_ahead(env_id, solver_id, dtype, B, K, substeps, props: Props, control: Optional[Control],
-              obs_stepsize: float, env_tau: float, state_in: Sequence[torch.Tensor], actions: torch.Tensor,
-              action_layout: int, obs_traj: torch.Tensor, state_traj: Optional[Sequence[torch.Tensor]],
-              traj_layout: int, last_state: Sequence[torch.Tensor], semantics: int,
-              workspace: Optional[torch.Tensor] = None, opts: Optional[LaunchOpts] = None, gym=None):
-    """gym: None or (reward, terminated, truncated) device tensors in the trajectory layout (excenv_traj_gym_t)."""
-    _require_device(obs_traj, "vmap_sim_ahead")
-    g = None
-    if gym is not None:
-        g = TrajGym(gym[0].data_ptr(), gym[1].data_ptr(), gym[2].data_ptr())
-    with _on_device(obs_traj.device):
-        stream = _raw_stream(obs_traj.device)
-        rc = lib().excenv_sim_ahead_ws(
-            ctypes.c_int(env_id), ctypes.c_int(solver_id), ctypes.c_int(dtype_id(dtype)), ctypes.c_int64(B),
-            ctypes.c_int64(K), ctypes.c_int32(substeps), ctypes.byref(props),
-            ctypes.byref(control) if control is not None else None, ctypes.c_double(obs_stepsize),
-            ctypes.c_double(env_tau), _ptrs(state_in), ctypes.c_void_p(actions.data_ptr() if K > 0 else None),
-            ctypes.c_int(action_layout), ctypes.c_void_p(obs_traj.data_ptr()),
-            _ptrs(state_traj) if state_traj is not None else None, ctypes.c_int(traj_layout), _ptrs(last_state),
-            ctypes.c_int(semantics), ctypes.byref(g) if g is not None else None,
-            ctypes.c_void_p(workspace.data_ptr() if workspace is not None else None),
-            ctypes.c_int64(workspace.numel() * workspace.element_size() if workspace is not None else 0),
-            _opts_ref(opts), ctypes.c_void_p(stream),
-        )
-    _check(rc, "excenv_sim_ahead")
-
-
-def sim_ahead_raw(env_id, solver_id, dtype_code, B, K, substeps, props_ref, control_ref, obs_stepsize, env_tau, in_ptrs,
-                  actions_ptr, action_layout, obs_ptr, traj_ptrs, traj_layout, last_ptrs, semantics, ws_ptr, ws_bytes, opts_ref,
-                  stream, gym_ref=None):
-    """excenv_sim_ahead_ws with every argument already in its C form (the fast path of vmap_sim_ahead: lane-major
-    trajectories; gym_ref: None or byref(TrajGym)). The caller has made the buffers' device current."""
-    rc = _lib.excenv_sim_ahead_ws(env_id, solver_id, dtype_code, B, K, substeps, props_ref, control_ref, obs_stepsize, env_tau,
-                                  in_ptrs, actions_ptr, action_layout, obs_ptr, traj_ptrs, traj_layout, last_ptrs, semantics,
-                                  gym_ref, ws_ptr, ws_bytes, opts_ref, stream)
-    if rc != 0:
-        _check(rc, "excenv_sim_ahead")
-
-
 def rew_trunc_term(env_id, dtype, B, rows, props: Props, control: Optional[Control], ref_strides: Optional[Sequence[int]],
                    state_traj: Sequence[torch.Tensor], s_sb: int, s_sk: int, reward: torch.Tensor, terminated: torch.Tensor,
                    truncated: torch.Tensor, out_layout: int):
     """excenv_rew_trunc_term: reward / terminated / truncated of a stored trajectory (one thread per (env, row))."""
-    _require_device(truncated, "vmap_generate_rew_trunc_term_ahead")
     rs = (ctypes.c_int64 * len(ref_strides))(*ref_strides) if ref_strides else None
-    with _on_device(truncated.device):
-        rc = lib().excenv_rew_trunc_term(
-            ctypes.c_int(env_id), ctypes.c_int(dtype_id(dtype)), ctypes.c_int64(B), ctypes.c_int64(rows), ctypes.byref(props),
-            ctypes.byref(control) if control is not None else None, rs, _ptrs(state_traj), ctypes.c_int64(s_sb),
-            ctypes.c_int64(s_sk), ctypes.c_void_p(reward.data_ptr() if rows > 1 else None),
-            ctypes.c_void_p(terminated.data_ptr() if rows > 1 else None), ctypes.c_void_p(truncated.data_ptr()),
-            ctypes.c_int(out_layout), ctypes.c_void_p(_raw_stream(truncated.device)))
-    _check(rc, "excenv_rew_trunc_term")
+    _launch("excenv_rew_trunc_term", truncated, "vmap_generate_rew_trunc_term_ahead", env_id, dtype_id(dtype), B, rows,
+            ctypes.byref(props), _ref(control), rs, _ptrs(state_traj), s_sb, s_sk, reward.data_ptr() if rows > 1 else None,
+            terminated.data_ptr() if rows > 1 else None, truncated.data_ptr(), out_layout)
 
 
 def state_from_observation(env_id, dtype, B, props: Props, control_idx: Sequence[int], obs: torch.Tensor,
                            state_out: Sequence[torch.Tensor], reference_out: Sequence[torch.Tensor]):
     """excenv_state_from_observation: obs [B, O + n_control] -> denormalised state leaves (+ controlled reference leaves)."""
-    _require_device(obs, "vmap_generate_state_from_observation")
     nc = len(control_idx)
-    with _on_device(obs.device):
-        rc = lib().excenv_state_from_observation(
-            ctypes.c_int(env_id), ctypes.c_int(dtype_id(dtype)), ctypes.c_int64(B), ctypes.byref(props), ctypes.c_int32(nc),
-            (ctypes.c_int32 * nc)(*control_idx) if nc else None, ctypes.c_void_p(obs.data_ptr()), _ptrs(state_out),
-            _ptrs(reference_out) if nc else None, ctypes.c_void_p(_raw_stream(obs.device)))
-    _check(rc, "excenv_state_from_observation")
+    _launch("excenv_state_from_observation", obs, "vmap_generate_state_from_observation", env_id, dtype_id(dtype), B,
+            ctypes.byref(props), nc, _i32s(control_idx), obs.data_ptr(), _ptrs(state_out), _ptrs(reference_out) if nc else None)
 
 
 def update_ref(env_id, dtype, B, props: Props, control_idx: Sequence[int], reference: Sequence[torch.Tensor],
@@ -429,23 +429,14 @@ def update_ref(env_id, dtype, B, props: Props, control_idx: Sequence[int], refer
     _require_device(keys, "GymWrapper.update_ref")
     assert keys.dtype == torch.int64 and keys.is_contiguous() and hold.dtype == torch.int64 and hold.is_contiguous()
     nc = len(control_idx)
-    with _on_device(keys.device):
-        rc = lib().excenv_update_ref(
-            ctypes.c_int(env_id), ctypes.c_int(dtype_id(dtype)), ctypes.c_int64(B), ctypes.byref(props), ctypes.c_int32(nc),
-            (ctypes.c_int32 * nc)(*control_idx) if nc else None, _ptrs(reference) if nc else None,
-            ctypes.c_void_p(keys.data_ptr()), ctypes.c_void_p(hold.data_ptr()), ctypes.c_int32(hold_min), ctypes.c_int32(hold_max),
-            ctypes.c_void_p(_raw_stream(keys.device)))
-    _check(rc, "excenv_update_ref")
+    _launch("excenv_update_ref", keys, "GymWrapper.update_ref", env_id, dtype_id(dtype), B, ctypes.byref(props), nc,
+            _i32s(control_idx), _ptrs(reference) if nc else None, keys.data_ptr(), hold.data_ptr(), hold_min, hold_max)
 
 
 def observe(env_id, dtype, B, props: Props, control: Optional[Control], state: Sequence[torch.Tensor], obs: torch.Tensor):
     """excenv_observe: generate_observation for a batch of states in one launch (obs: [B, O + n_control] row-major)."""
-    _require_device(obs, "generate_observation")
-    with _on_device(obs.device):
-        rc = lib().excenv_observe(ctypes.c_int(env_id), ctypes.c_int(dtype_id(dtype)), ctypes.c_int64(B), ctypes.byref(props),
-                                  ctypes.byref(control) if control is not None else None, _ptrs(state),
-                                  ctypes.c_void_p(obs.data_ptr()), ctypes.c_void_p(_raw_stream(obs.device)))
-    _check(rc, "excenv_observe")
+    _launch("excenv_observe", obs, "generate_observation", env_id, dtype_id(dtype), B, ctypes.byref(props), _ref(control),
+            _ptrs(state), obs.data_ptr())
 
 
 def update_ref_to(env_id, dtype, B, props: Props, control_idx: Sequence[int], reference_in: Sequence[torch.Tensor],
@@ -456,34 +447,17 @@ def update_ref_to(env_id, dtype, B, props: Props, control_idx: Sequence[int], re
     for t in (keys_in, hold_in, keys_out, hold_out):
         assert t.dtype == torch.int64 and t.is_contiguous()
     nc = len(control_idx)
-    with _on_device(keys_in.device):
-        rc = lib().excenv_update_ref_to(
-            ctypes.c_int(env_id), ctypes.c_int(dtype_id(dtype)), ctypes.c_int64(B), ctypes.byref(props), ctypes.c_int32(nc),
-            (ctypes.c_int32 * nc)(*control_idx) if nc else None, _ptrs(reference_in) if nc else None,
-            ctypes.c_void_p(keys_in.data_ptr()), ctypes.c_void_p(hold_in.data_ptr()), _ptrs(reference_out) if nc else None,
-            ctypes.c_void_p(keys_out.data_ptr()), ctypes.c_void_p(hold_out.data_ptr()), ctypes.c_int32(hold_min),
-            ctypes.c_int32(hold_max), ctypes.c_void_p(_raw_stream(keys_in.device)))
-    _check(rc, "excenv_update_ref_to")
+    _launch("excenv_update_ref_to", keys_in, "GymWrapper.update_ref", env_id, dtype_id(dtype), B, ctypes.byref(props), nc,
+            _i32s(control_idx), _ptrs(reference_in) if nc else None, keys_in.data_ptr(), hold_in.data_ptr(),
+            _ptrs(reference_out) if nc else None, keys_out.data_ptr(), hold_out.data_ptr(), hold_min, hold_max)
 
 
 def random_state(env_id, dtype, B, props: Props, keys: torch.Tensor, state_out: Sequence[torch.Tensor], key_leaf: torch.Tensor):
     """excenv_random_state: init_state(key) for every environment in one launch (keys / key_leaf: int64 [B, 2])."""
     _require_device(keys, "vmap_init_state")
     assert keys.dtype == torch.int64 and keys.is_contiguous() and key_leaf.dtype == torch.int64 and key_leaf.is_contiguous()
-    with _on_device(keys.device):
-        rc = lib().excenv_random_state(
-            ctypes.c_int(env_id), ctypes.c_int(dtype_id(dtype)), ctypes.c_int64(B), ctypes.byref(props),
-            ctypes.c_void_p(keys.data_ptr()), _ptrs(state_out), ctypes.c_void_p(key_leaf.data_ptr()),
-            ctypes.c_void_p(_raw_stream(keys.device)))
-    _check(rc, "excenv_random_state")
-
-
-def sim_ahead_workspace_bytes(env_id, dtype, B, K, substeps, n_control, action_layout, traj_layout,
-                              with_state_traj=True) -> int:
-    return int(lib().excenv_sim_ahead_workspace_bytes(
-        ctypes.c_int(env_id), ctypes.c_int(dtype_id(dtype)), ctypes.c_int64(B), ctypes.c_int64(K),
-        ctypes.c_int32(substeps), ctypes.c_int32(n_control), ctypes.c_int(action_layout), ctypes.c_int(traj_layout),
-        ctypes.c_int(int(with_state_traj))))
+    _launch("excenv_random_state", keys, "vmap_init_state", env_id, dtype_id(dtype), B, ctypes.byref(props), keys.data_ptr(),
+            _ptrs(state_out), key_leaf.data_ptr())
 
 
 def transpose(x: torch.Tensor) -> torch.Tensor:
@@ -491,11 +465,7 @@ def transpose(x: torch.Tensor) -> torch.Tensor:
     _require_device(x, "transpose")
     assert x.ndim == 2 and x.is_contiguous()
     out = torch.empty((x.shape[1], x.shape[0]), dtype=x.dtype, device=x.device)
-    with torch.cuda.device(x.device):
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        rc = lib().excenv_transpose(ctypes.c_int(dtype_id(x.dtype)), ctypes.c_int64(x.shape[0]), ctypes.c_int64(x.shape[1]),
-                                    ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(stream))
-    _check(rc, "excenv_transpose")
+    _launch("excenv_transpose", x, "transpose", dtype_id(x.dtype), x.shape[0], x.shape[1], x.data_ptr(), out.data_ptr())
     return out
 
 
@@ -503,12 +473,7 @@ def probe_math(which: int, x: torch.Tensor) -> torch.Tensor:
     _require_device(x, "probe_math")
     x = x.contiguous()
     out = torch.empty_like(x)
-    with torch.cuda.device(x.device):
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        rc = lib().excenv_probe_math(ctypes.c_int(which), ctypes.c_int(dtype_id(x.dtype)), ctypes.c_int64(x.numel()),
-                                     ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(out.data_ptr()),
-                                     ctypes.c_void_p(stream))
-    _check(rc, "excenv_probe_math")
+    _launch("excenv_probe_math", x, "probe_math", which, dtype_id(x.dtype), x.numel(), x.data_ptr(), out.data_ptr())
     return out
 
 
@@ -518,10 +483,6 @@ def probe_div(num: torch.Tensor, den: torch.Tensor):
     num, den = num.contiguous(), den.contiguous()
     assert num.shape == den.shape and num.dtype == den.dtype
     fast, ref = torch.empty_like(num), torch.empty_like(num)
-    with torch.cuda.device(num.device):
-        stream = torch.cuda.current_stream(num.device).cuda_stream
-        rc = lib().excenv_probe_div(ctypes.c_int(dtype_id(num.dtype)), ctypes.c_int64(num.numel()), ctypes.c_void_p(num.data_ptr()),
-                                    ctypes.c_void_p(den.data_ptr()), ctypes.c_void_p(fast.data_ptr()),
-                                    ctypes.c_void_p(ref.data_ptr()), ctypes.c_void_p(stream))
-    _check(rc, "excenv_probe_div")
+    _launch("excenv_probe_div", num, "probe_div", dtype_id(num.dtype), num.numel(), num.data_ptr(), den.data_ptr(),
+            fast.data_ptr(), ref.data_ptr())
     return fast, ref

@@ -24,6 +24,7 @@ import numpy as np
 import torch
 
 from . import _native
+from ._native import cuda_get_device as _cuda_get_device, cuda_is_capturing as _cuda_is_capturing
 from . import random as _random
 from ._placement import StepSlotPool, TrajectoryPlacement
 from ._trajectory import TrajectoryLaunchMixin
@@ -39,11 +40,6 @@ def _is_scalar(x) -> bool:
     if isinstance(x, (bool, int, float, np.generic)):
         return True
     return _is_array(x) and x.ndim == 0
-
-
-# private fast accessors of torch when this build has them, the public (slower) API otherwise
-_cuda_get_device = getattr(torch._C, "_cuda_getDevice", None) or torch.cuda.current_device
-_cuda_is_capturing = getattr(torch._C, "_cuda_isCurrentStreamCapturing", None) or torch.cuda.is_current_stream_capturing
 
 
 class CoreEnvironment(TrajectoryLaunchMixin, ABC):

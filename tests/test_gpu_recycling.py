@@ -124,7 +124,7 @@ def test_gym_wrapper_loop_recycles_and_keeps_its_results():
 @pytest.mark.parametrize("actions_layout", ["row_major", "lane_major"])
 def test_sim_ahead_single_allocation_outputs_equal_separately_allocated_ones(actions_layout):
     """vmap_sim_ahead carves observations, state trajectories and last_state of small problems out of one allocation
-    (core_env.py _run_sim_ahead_lane_major); same values as with one allocation per array, shapes / strides as before, and a
+    (_trajectory.py _outputs_shared); same values as with one allocation per array, shapes / strides as before, and a
     later call never touches what an earlier one returned."""
     env, state, _ = _env("PMSM")
     K = 12
