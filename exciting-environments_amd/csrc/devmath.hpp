@@ -241,4 +241,54 @@ __device__ __forceinline__ float cos_t(float x) { float s, c; sincos_t(x, s, c);
 __device__ __forceinline__ double sin_t(double x) { return ::sin(x); }
 __device__ __forceinline__ double cos_t(double x) { return ::cos(x); }
 
+// ---- fp64 sin / cos for the reverse-mode kernels (kernels_vjp.hpp) ---------------------------------------------------------------
+// The device library's fp64 sincos carries its full-range (Payne-Hanek) path inline: some hundred registers and a few KB per call
+// site, and an RK adjoint in fp64 has up to 36 of them. The reverse pass evaluates Jacobians at saved (wrapped) angles and stage
+// states next to them, so a two-constant Cody-Waite reduction by pi/2 (fdlibm's pio2_1 / pio2_1t; n * pio2_1 is exact for
+// |n| < 2^20, i.e. |x| < 1.6e6) and fdlibm's kernel polynomials do: absolute error <= 2e-16 in that range — a Jacobian moved by
+// rounding only. Straight-line on purpose (no range test, no call): beyond that range the reduction loses accuracy gradually
+// (the only unwrapped angle the reverse pass can meet is a caller's own initial angle in row 0 under the step semantics); NaN and
+// inf give NaN. The forward kernels keep the library's routine (their bits are pinned against the oracle).
+__device__ __forceinline__ void sincos_lean(double x, double& s, double& c) {
+  const double n = __builtin_rint(x * 6.36619772367581382433e-01);  // x * 2/pi
+  double r = xfma(-n, 1.57079632673412561417e+00, x);
+  r = xfma(-n, 6.07710050650619224932e-11, r);
+  const int q = (int)n;
+  const double z = r * r;
+  double ps = xfma(1.58969099521155010221e-10, z, -2.50507602534068634195e-08);
+  ps = xfma(ps, z, 2.75573137070700676789e-06);
+  ps = xfma(ps, z, -1.98412698298579493134e-04);
+  ps = xfma(ps, z, 8.33333333332248946124e-03);
+  ps = xfma(ps, z, -1.66666666666666324348e-01);
+  const double sr = xfma(ps * z, r, r);
+  double pc = xfma(-1.13596475577881948265e-11, z, 2.08757232129817482790e-09);
+  pc = xfma(pc, z, -2.75573143513906633035e-07);
+  pc = xfma(pc, z, 2.48015872894767294178e-05);
+  pc = xfma(pc, z, -1.38888888888741095749e-03);
+  pc = xfma(pc, z, 4.16666666666666019037e-02);
+  const double hz = 0.5 * z;
+  const double a = 1.0 - hz;
+  const double cr = a + (((1.0 - a) - hz) + z * (z * pc));
+  const double s0 = (q & 1) ? cr : sr;
+  const double c0 = (q & 1) ? sr : cr;
+  s = (q & 2) ? -s0 : s0;
+  c = ((q + 1) & 2) ? -c0 : c0;
+}
+// sin / cos as the model functions call them: LEAN selects the routine above for fp64 (nothing else changes)
+template <bool LEAN> __device__ __forceinline__ void sincos_x(float x, float& s, float& c) { sincos_t(x, s, c); }
+template <bool LEAN> __device__ __forceinline__ void sincos_x(double x, double& s, double& c) {
+  if constexpr (LEAN) sincos_lean(x, s, c);
+  else sincos_t(x, s, c);
+}
+template <bool LEAN> __device__ __forceinline__ float sin_x(float x) { return sin_t(x); }
+template <bool LEAN> __device__ __forceinline__ float cos_x(float x) { return cos_t(x); }
+template <bool LEAN> __device__ __forceinline__ double sin_x(double x) {
+  if constexpr (LEAN) { double s, c; sincos_lean(x, s, c); return s; }
+  else return sin_t(x);
+}
+template <bool LEAN> __device__ __forceinline__ double cos_x(double x) {
+  if constexpr (LEAN) { double s, c; sincos_lean(x, s, c); return c; }
+  else return cos_t(x);
+}
+
 }  // namespace excenv

@@ -292,6 +292,74 @@ int excenv_sim_ahead(int env, int solver, int dtype, int64_t B, int64_t K, int32
                              stream);
 }
 
+int64_t excenv_sim_ahead_vjp_workspace_bytes(int env, int dtype, int64_t B, int64_t K, int action_layout) {
+  const EnvVTable* t = table_public(env);
+  if (!t || B < 0 || K < 0) return -1;
+  return vjp_workspace_bytes(t->A, dtype == EXCENV_F64 ? 8 : 4, B, K, action_layout);
+}
+
+int excenv_sim_ahead_vjp(int env, int solver, int dtype, int64_t B, int64_t K, int32_t substeps,
+                         const excenv_props_t* props, const excenv_control_t* control, double obs_stepsize,
+                         double env_tau, const void* actions, int action_layout, const void* const* state_traj,
+                         const void* grad_obs_traj, const void* const* grad_state_traj,
+                         const void* const* grad_last_state, void* grad_actions, void* const* grad_state_in,
+                         int semantics, void* workspace, int64_t workspace_bytes, const excenv_launch_opts_t* opts,
+                         void* stream) {
+  const char* fn = "excenv_sim_ahead_vjp";
+  if (int rc = check_common(fn, env, solver, dtype, B)) return rc;
+  if (K < 0 || substeps < 1) { set_error("%s: bad K=%lld or substeps=%d", fn, (long long)K, substeps); return EXCENV_EINVAL; }
+  if (semantics == EXCENV_SEM_AHEAD_ACCUMULATED_T) {
+    set_error("%s: EXCENV_SEM_AHEAD_ACCUMULATED_T has no reverse mode (use EXCENV_SEM_AHEAD or EXCENV_SEM_STEP)", fn);
+    return EXCENV_EUNSUPPORTED;
+  }
+  if (semantics != EXCENV_SEM_STEP && semantics != EXCENV_SEM_AHEAD) { set_error("%s: bad semantics %d", fn, semantics); return EXCENV_EINVAL; }
+  if (action_layout == EXCENV_LAYOUT_TILED) { set_error("%s: the tiled layout has no reverse mode (lane-major or env-major actions)", fn); return EXCENV_EUNSUPPORTED; }
+  if (action_layout != EXCENV_LAYOUT_ENV_MAJOR && action_layout != EXCENV_LAYOUT_LANE_MAJOR) { set_error("%s: bad layout id", fn); return EXCENV_EINVAL; }
+  if (!props || !state_traj || !grad_state_in || ((!actions || !grad_actions) && K > 0)) { set_error("%s: NULL argument", fn); return EXCENV_ENULL; }
+  if (props->pmsm_lut) { set_error("%s: the saturated PMSM (pmsm_lut) has no reverse mode", fn); return EXCENV_EUNSUPPORTED; }
+  const EnvVTable* t = table_public(env);
+  const int nc = control ? control->n_control : 0;
+  if (nc < 0 || nc > EXCENV_MAX_CONTROL) { set_error("%s: bad n_control %d", fn, nc); return EXCENV_EINVAL; }
+  if (int rc = check_opts(fn, opts)) return rc;
+  {
+    bool per_env = false;
+    for (int j = 0; j < t->P; ++j) per_env |= props->static_params[j].per_env != nullptr;
+    for (int j = 0; j < t->S; ++j) per_env |= props->state_min[j].per_env != nullptr || props->state_max[j].per_env != nullptr;
+    for (int j = 0; j < t->A; ++j) per_env |= props->action_min[j].per_env != nullptr || props->action_max[j].per_env != nullptr;
+    if (per_env) { set_error("%s: per-environment property arrays are not supported (broadcast properties only)", fn); return EXCENV_EUNSUPPORTED; }
+  }
+  const int elem = dtype == EXCENV_F64 ? 8 : 4;
+  const void* k_actions = actions;
+  const bool transposed = action_layout == EXCENV_LAYOUT_ENV_MAJOR && B > 0 && K > 0;
+  if (transposed) {
+    const int64_t need = vjp_workspace_bytes(t->A, elem, B, K, action_layout);
+    if (!workspace || workspace_bytes < need) {
+      set_error("%s: env-major actions need a workspace of %lld bytes (excenv_sim_ahead_vjp_workspace_bytes)", fn, (long long)need);
+      return EXCENV_EINVAL;
+    }
+    k_actions = workspace;
+  }
+  // the wide form: whole lanes and 16-byte accesses everywhere
+  bool wide_ok = (B % (16 / elem)) == 0 && align_of(k_actions) >= 16 && align_of(grad_actions) >= 16 && align_of(grad_obs_traj) >= 16;
+  for (int j = 0; j < t->S; ++j) {
+    if (!state_traj[j] || !grad_state_in[j]) { set_error("%s: state pointer %d is NULL", fn, j); return EXCENV_ENULL; }
+    wide_ok = wide_ok && align_of(state_traj[j]) >= 16 && align_of(grad_state_in[j]) >= 16 &&
+              (!grad_state_traj || align_of(grad_state_traj[j]) >= 16) && (!grad_last_state || align_of(grad_last_state[j]) >= 16);
+  }
+  const int V = vjp_envs_per_lane(env, solver, B, elem, opts->envs_per_lane, wide_ok);
+  if (V == 0 || !vjp_instantiated(semantics, env, elem, solver, false, V)) {
+    set_error("%s: opts.envs_per_lane = %d is not available (1, or %d where the model and solver have that form, with batch_size %% %d == 0 and 16-byte aligned arrays)", fn,
+              opts->envs_per_lane, 16 / elem, 16 / elem);
+    return EXCENV_EINVAL;
+  }
+  if (transposed) {
+    if (int rc = launch_transpose(dtype, B, K * t->A, actions, workspace, (hipStream_t)stream)) { set_error("%s: action transpose failed", fn); return rc; }
+  }
+  const VjpCall vc{solver, dtype, B, K, substeps, nc, props, obs_stepsize, env_tau, semantics, k_actions, state_traj, grad_obs_traj,
+                   grad_state_traj, grad_last_state, grad_actions, grad_state_in, V, stream};
+  return t->sim_vjp(vc);
+}
+
 int excenv_rew_trunc_term(int env, int dtype, int64_t B, int64_t rows, const excenv_props_t* props,
                           const excenv_control_t* control, const int64_t* ref_strides, const void* const* state_traj,
                           int64_t state_env_stride, int64_t state_row_stride, void* reward, uint8_t* terminated,

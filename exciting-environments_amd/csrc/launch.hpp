@@ -7,6 +7,7 @@
 #include <type_traits>
 #include "kernels_emr.hpp"
 #include "refgen.hpp"
+#include "vjp.hpp"
 
 namespace excenv {
 
@@ -129,7 +130,19 @@ struct EnvVTable {
   int (*update_ref)(const RefGenCall&);
   int (*random_state)(const RandomStateCall&);
   int (*observe)(const ObserveCall&);
+  int (*sim_vjp)(const VjpCall&);  // reverse mode of sim (kernels_vjp.hpp)
 };
+
+// The reverse-mode launcher of a model: declared here so that it sits in the same table as every other entry point, defined in the
+// model's own translation unit vjp_<model>.hip (the saturated PMSM's reports that it has none)
+template <template <typename> class MT> int vjp_entry(const VjpCall&);
+template <> int vjp_entry<Pendulum>(const VjpCall&);
+template <> int vjp_entry<MassSpringDamper>(const VjpCall&);
+template <> int vjp_entry<CartPole>(const VjpCall&);
+template <> int vjp_entry<Acrobot>(const VjpCall&);
+template <> int vjp_entry<FluidTank>(const VjpCall&);
+template <> int vjp_entry<Pmsm>(const VjpCall&);
+template <> int vjp_entry<PmsmSat>(const VjpCall&);
 
 template <typename T, class M>
 static bool fill_props(KProps<T, M>& kp, const excenv_props_t* p) {
@@ -668,7 +681,7 @@ template <template <typename> class MT> struct EnvEntry {
   }
   static EnvVTable vtable() {
     return EnvVTable{MT<float>::S, MT<float>::A, MT<float>::O, MT<float>::P, &step, &sim, &traj_gym, &from_obs, &update_ref,
-                     &random_state, &observe};
+                     &random_state, &observe, &vjp_entry<MT>};
   }
 };
 

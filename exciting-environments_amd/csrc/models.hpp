@@ -57,6 +57,25 @@ template <typename T, class M> __device__ __forceinline__ void prep_ctx(Ctx<T, M
   M::prep(c);
 }
 
+// ---- reverse mode (vjp.hpp, kernels_vjp.hpp) --------------------------------------------------------------------------------
+// Every model carries, next to f / post / observe, their transposed Jacobians at a given point:
+//   f_vjp(y, u, c, st, fb, yb, ub, wb): yb = (df/dy)^T fb, ub = (df/du)^T fb (both overwritten), wb += (df/d omega_el)^T fb (PMSM)
+//   post_vjp(sv, c, r): r <- (d post / d st)^T r at the saved (post-processed) row sv
+//   observe_vjp(sv, c, gob, r): r += (d observe / d st)^T gob
+// Subgradient conventions: a clamp / clip has derivative 0 on its boundary, sign_of has derivative 0, the tank's
+// sqrt term has derivative 0 where h <= 0. The InvDiv denominators of the forward are reused.
+// Transpose of normalize_field: d ob / d x = 2 / (smax - smin)
+template <typename T, class M> __device__ __forceinline__ T normalize_field_vjp(const Ctx<T, M>& c, int j, T g) {
+  return c.nrm[j].div(T(2) * g, c.fastdiv);
+}
+// observation = every state field normalised, in order (the five models other than PMSM)
+template <typename T, class M>
+__device__ __forceinline__ void observe_fields_vjp(const Ctx<T, M>& c, const T (&gob)[M::O], T (&r)[M::S]) {
+  static_assert(M::O == M::S, "observation = the normalised state");
+#pragma unroll
+  for (int j = 0; j < M::S; ++j) r[j] = r[j] + normalize_field_vjp(c, j, gob[j]);
+}
+
 // ---- Pendulum: pendulum_env.py:144-150,188 ; P = (g,l,m) --------------------------------
 template <typename T> struct Pendulum {
   static constexpr int ID = EXCENV_PENDULUM, S = 2, A = 1, O = 2, P = 3, NY = 2, ND = 1;
@@ -66,10 +85,22 @@ template <typename T> struct Pendulum {
   __device__ static __forceinline__ void prep(C& c) { c.den[0].init(c.P[2] * (c.P[1] * c.P[1]), c.fastdiv); }  // m * (l * l)
   __device__ static __forceinline__ void get_y(const T (&st)[S], T (&y)[NY]) { y[0] = st[0]; y[1] = st[1]; }
   __device__ static __forceinline__ void set_y(T (&st)[S], const T (&y)[NY]) { st[0] = y[0]; st[1] = y[1]; }
-  __device__ static __forceinline__ void f(const T (&y)[NY], const T (&u)[A], const C& c, const T (&)[S], T (&dy)[NY]) {
+  template <bool LEAN = false> __device__ static __forceinline__ void f(const T (&y)[NY], const T (&u)[A], const C& c, const T (&)[S], T (&dy)[NY]) {
     const T g = c.P[0], l = c.P[1], m = c.P[2];
-    dy[1] = c.den[0].div(u[0] + l * m * g * sin_t(y[0]), c.fastdiv);  // / (m * (l * l))
+    dy[1] = c.den[0].div(u[0] + l * m * g * sin_x<LEAN>(y[0]), c.fastdiv);  // / (m * (l * l))
     dy[0] = y[1];
+  }
+  template <bool LEAN = false> __device__ static __forceinline__ void f_vjp(const T (&y)[NY], const T (&)[A], const C& c, const T (&)[S], const T (&fb)[NY],
+                                               T (&yb)[NY], T (&ub)[A], T&) {
+    const T g = c.P[0], l = c.P[1], m = c.P[2];
+    const T q = c.den[0].div(fb[1], c.fastdiv);  // fb[1] / (m * (l * l))
+    yb[0] = q * (l * m * g * cos_x<LEAN>(y[0]));
+    yb[1] = fb[0];
+    ub[0] = q;
+  }
+  __device__ static __forceinline__ void post_vjp(const T (&)[S], const C&, T (&)[S]) {}  // wrap: derivative 1
+  template <bool LEAN = false> __device__ static __forceinline__ void observe_vjp(const T (&)[S], const C& c, const T (&gob)[O], T (&r)[S]) {
+    observe_fields_vjp<T, Pendulum>(c, gob, r);
   }
   __device__ static __forceinline__ void post(T (&st)[S], const C&) { st[0] = wrap_angle(st[0]); }
   __device__ static __forceinline__ void observe(const T (&st)[S], const C& c, T (&ob)[O]) {
@@ -87,10 +118,22 @@ template <typename T> struct MassSpringDamper {
   __device__ static __forceinline__ void prep(C& c) { c.den[0].init(c.P[2], c.fastdiv); }  // m
   __device__ static __forceinline__ void get_y(const T (&st)[S], T (&y)[NY]) { y[0] = st[0]; y[1] = st[1]; }
   __device__ static __forceinline__ void set_y(T (&st)[S], const T (&y)[NY]) { st[0] = y[0]; st[1] = y[1]; }
-  __device__ static __forceinline__ void f(const T (&y)[NY], const T (&u)[A], const C& c, const T (&)[S], T (&dy)[NY]) {
+  template <bool LEAN = false> __device__ static __forceinline__ void f(const T (&y)[NY], const T (&u)[A], const C& c, const T (&)[S], T (&dy)[NY]) {
     const T d = c.P[0], k = c.P[1];
     dy[1] = c.den[0].div(u[0] - d * y[1] - k * y[0], c.fastdiv);  // / m
     dy[0] = y[1];
+  }
+  template <bool LEAN = false> __device__ static __forceinline__ void f_vjp(const T (&)[NY], const T (&)[A], const C& c, const T (&)[S], const T (&fb)[NY],
+                                               T (&yb)[NY], T (&ub)[A], T&) {
+    const T d = c.P[0], k = c.P[1];
+    const T q = c.den[0].div(fb[1], c.fastdiv);  // fb[1] / m
+    yb[0] = -(k * q);
+    yb[1] = fb[0] - d * q;
+    ub[0] = q;
+  }
+  __device__ static __forceinline__ void post_vjp(const T (&)[S], const C&, T (&)[S]) {}
+  template <bool LEAN = false> __device__ static __forceinline__ void observe_vjp(const T (&)[S], const C& c, const T (&gob)[O], T (&r)[S]) {
+    observe_fields_vjp<T, MassSpringDamper>(c, gob, r);
   }
   __device__ static __forceinline__ void post(T (&)[S], const C&) {}
   __device__ static __forceinline__ void observe(const T (&st)[S], const C& c, T (&ob)[O]) {
@@ -117,11 +160,11 @@ template <typename T> struct CartPole {
 #pragma unroll
     for (int j = 0; j < 4; ++j) st[j] = y[j];
   }
-  __device__ static __forceinline__ void f(const T (&y)[NY], const T (&u)[A], const C& c, const T (&)[S], T (&dy)[NY]) {
+  template <bool LEAN = false> __device__ static __forceinline__ void f(const T (&y)[NY], const T (&u)[A], const C& c, const T (&)[S], T (&dy)[NY]) {
     const T mu_p = c.P[0], mu_c = c.P[1], l = c.P[2], m_p = c.P[3], g = c.P[5];
     const T velocity = y[1], theta = y[2], omega = y[3];
     T s, co;
-    sincos_t(theta, s, co);
+    sincos_x<LEAN>(theta, s, co);
     const auto& by_mass = c.den[0];  // / (m_c + m_p)
     const T d_omega =
         (g * s + co * by_mass.div(-u[0] - m_p * l * (omega * omega) * s + mu_c * sign_of(velocity), c.fastdiv) -
@@ -132,6 +175,46 @@ template <typename T> struct CartPole {
     dy[1] = d_velocity;
     dy[2] = omega;
     dy[3] = d_omega;
+  }
+  // reverse sweep over the expression tree of f, same grouping (sign_of: derivative 0)
+  template <bool LEAN = false> __device__ static __forceinline__ void f_vjp(const T (&y)[NY], const T (&u)[A], const C& c, const T (&)[S], const T (&fb)[NY],
+                                               T (&yb)[NY], T (&ub)[A], T&) {
+    const T mu_p = c.P[0], mu_c = c.P[1], l = c.P[2], m_p = c.P[3], g = c.P[5];
+    const T velocity = y[1], theta = y[2], omega = y[3];
+    T s, co;
+    sincos_x<LEAN>(theta, s, co);
+    const auto& by_mass = c.den[0];  // / (m_c + m_p)
+    const T a_n = by_mass.div(-u[0] - m_p * l * (omega * omega) * s + mu_c * sign_of(velocity), c.fastdiv);
+    const T den_w = l * (T(4.0 / 3.0) - by_mass.div(m_p * (co * co), c.fastdiv));
+    const T d_omega = (g * s + co * a_n - c.den[1].div(mu_p * omega, c.fastdiv)) / den_w;
+    // d_velocity = (u + m_p l (omega^2 s - d_omega co) - mu_c sign) / (m_c + m_p)
+    const T t = by_mass.div(fb[1], c.fastdiv);
+    const T inner_b = t * (m_p * l);
+    T u_b = t;
+    T omega_b = fb[2] + inner_b * (T(2) * omega * s);
+    T s_b = inner_b * (omega * omega);
+    T co_b = -(inner_b * d_omega);
+    const T dw_b = fb[3] - inner_b * co;
+    // d_omega = num / den_w
+    const T num_b = dw_b / den_w;
+    const T den_b = -(num_b * d_omega);
+    co_b = co_b - den_b * (l * by_mass.div(m_p * (T(2) * co), c.fastdiv));
+    s_b = s_b + num_b * g;
+    co_b = co_b + num_b * a_n;
+    omega_b = omega_b - c.den[1].div(mu_p * num_b, c.fastdiv);
+    const T n1_b = by_mass.div(num_b * co, c.fastdiv);
+    u_b = u_b - n1_b;
+    omega_b = omega_b - n1_b * (m_p * l * (T(2) * omega * s));
+    s_b = s_b - n1_b * (m_p * l * (omega * omega));
+    yb[0] = T(0);
+    yb[1] = fb[0];
+    yb[2] = s_b * co - co_b * s;
+    yb[3] = omega_b;
+    ub[0] = u_b;
+  }
+  __device__ static __forceinline__ void post_vjp(const T (&)[S], const C&, T (&)[S]) {}
+  template <bool LEAN = false> __device__ static __forceinline__ void observe_vjp(const T (&)[S], const C& c, const T (&gob)[O], T (&r)[S]) {
+    observe_fields_vjp<T, CartPole>(c, gob, r);
   }
   __device__ static __forceinline__ void post(T (&st)[S], const C&) { st[2] = wrap_angle(st[2]); }
   __device__ static __forceinline__ void observe(const T (&st)[S], const C& c, T (&ob)[O]) {
@@ -155,11 +238,11 @@ template <typename T> struct Acrobot {
 #pragma unroll
     for (int j = 0; j < 4; ++j) st[j] = y[j];
   }
-  __device__ static __forceinline__ void f(const T (&y)[NY], const T (&u)[A], const C& c, const T (&)[S], T (&dy)[NY]) {
+  template <bool LEAN = false> __device__ static __forceinline__ void f(const T (&y)[NY], const T (&u)[A], const C& c, const T (&)[S], T (&dy)[NY]) {
     const T g = c.P[0], l_1 = c.P[1], m_1 = c.P[3], m_2 = c.P[4], l_c1 = c.P[5], l_c2 = c.P[6], I_1 = c.P[7], I_2 = c.P[8];
     const T theta_1 = y[0], theta_2 = y[1], omega_1 = y[2], omega_2 = y[3];
     T s2, c2;
-    sincos_t(theta_2, s2, c2);
+    sincos_x<LEAN>(theta_2, s2, c2);
     const T d_11 = m_1 * (l_c1 * l_c1) + m_2 * (l_1 * l_1 + l_c2 * l_c2 + T(2) * l_1 * l_c2 * c2) + I_1 + I_2;
     const T d_12 = m_2 * (l_c2 * l_c2 + l_1 * l_c2 * c2) + I_2;
     const T d_22 = m_2 * (l_c2 * l_c2) + I_2;
@@ -167,8 +250,8 @@ template <typename T> struct Acrobot {
     const T h_2 = m_2 * l_1 * l_c2 * s2 * (omega_1 * omega_1);
     // the reference's expressions literally (acrobot_env.py:182-183): theta + pi/2 rounds first. The angle-sum identities are 5 %
     // faster for Tsit5 fp32 but do not reproduce that rounding at unwrapped angles
-    const T cA = cos_t(theta_1 + K<T>::half_pi);
-    const T cB = cos_t(theta_1 + theta_2 + K<T>::half_pi);
+    const T cA = cos_x<LEAN>(theta_1 + K<T>::half_pi);
+    const T cB = cos_x<LEAN>(theta_1 + theta_2 + K<T>::half_pi);
     const T phi_1 = (m_1 * l_c1 + m_2 * l_1) * g * cA + m_2 * l_c2 * g * cB;
     const T phi_2 = m_2 * l_c2 * g * cB;
     const T d_omega_1 = T(1) / (d_12 - d_22 / d_12 * d_11) * (u[0] + d_22 / d_12 * (h_1 + phi_1) - h_2 - phi_2);
@@ -177,6 +260,65 @@ template <typename T> struct Acrobot {
     dy[1] = omega_2;
     dy[2] = d_omega_1;
     dy[3] = d_omega_2;
+  }
+  // reverse sweep over the expression tree of f, same grouping
+  template <bool LEAN = false> __device__ static __forceinline__ void f_vjp(const T (&y)[NY], const T (&u)[A], const C& c, const T (&)[S], const T (&fb)[NY],
+                                               T (&yb)[NY], T (&ub)[A], T&) {
+    const T g = c.P[0], l_1 = c.P[1], m_1 = c.P[3], m_2 = c.P[4], l_c1 = c.P[5], l_c2 = c.P[6], I_1 = c.P[7], I_2 = c.P[8];
+    const T theta_1 = y[0], theta_2 = y[1], omega_1 = y[2], omega_2 = y[3];
+    T s2, c2;
+    sincos_x<LEAN>(theta_2, s2, c2);
+    const T kap = m_2 * l_1 * l_c2;
+    const T d_11 = m_1 * (l_c1 * l_c1) + m_2 * (l_1 * l_1 + l_c2 * l_c2 + T(2) * l_1 * l_c2 * c2) + I_1 + I_2;
+    const T d_12 = m_2 * (l_c2 * l_c2 + l_1 * l_c2 * c2) + I_2;
+    const T d_22 = m_2 * (l_c2 * l_c2) + I_2;
+    const T h_1 = -kap * s2 * (omega_2 * omega_2) - T(2) * kap * s2 * omega_1 * omega_2;
+    T sA, cA, sB, cB;
+    sincos_x<LEAN>(theta_1 + K<T>::half_pi, sA, cA);
+    sincos_x<LEAN>(theta_1 + theta_2 + K<T>::half_pi, sB, cB);
+    const T al = (m_1 * l_c1 + m_2 * l_1) * g, be = m_2 * l_c2 * g;
+    const T phi_1 = al * cA + be * cB;
+    const T h_2 = kap * s2 * (omega_1 * omega_1);
+    const T phi_2 = be * cB;
+    const T r = d_22 / d_12;
+    const T den = d_12 - r * d_11;
+    const T d_omega_1 = T(1) / den * (u[0] + r * (h_1 + phi_1) - h_2 - phi_2);
+    const T d_omega_2 = (-d_11 * d_omega_1 - h_1 - phi_1) / d_12;
+    // d_omega_2 = Q / d_12, Q = -d_11 d_omega_1 - h_1 - phi_1
+    const T q_b = fb[3] / d_12;
+    T d12_b = -(q_b * d_omega_2);
+    T d11_b = -(q_b * d_omega_1);
+    const T b1 = fb[2] - q_b * d_11;
+    T h1_b = -q_b, phi1_b = -q_b;
+    // d_omega_1 = W / den
+    const T w_b = b1 / den;
+    const T den_b = -(w_b * d_omega_1);
+    T r_b = w_b * (h_1 + phi_1);
+    h1_b = h1_b + w_b * r;
+    phi1_b = phi1_b + w_b * r;
+    const T h2_b = -w_b, phi2_b = -w_b;
+    d12_b = d12_b + den_b;
+    r_b = r_b - den_b * d_11;
+    d11_b = d11_b - den_b * r;
+    d12_b = d12_b - r_b * r / d_12;
+    const T cA_b = phi1_b * al;
+    const T cB_b = phi1_b * be + phi2_b * be;
+    const T th1_b = -(cA_b * sA) - cB_b * sB;
+    T th2_b = -(cB_b * sB);
+    const T s2_b = h1_b * (-kap * (omega_2 * omega_2) - T(2) * kap * omega_1 * omega_2) + h2_b * (kap * (omega_1 * omega_1));
+    const T om2_b = h1_b * (-T(2) * kap * s2 * omega_2 - T(2) * kap * s2 * omega_1);
+    const T om1_b = h1_b * (-T(2) * kap * s2 * omega_2) + h2_b * (T(2) * kap * s2 * omega_1);
+    const T c2_b = d11_b * (T(2) * kap) + d12_b * kap;
+    th2_b = th2_b + s2_b * c2 - c2_b * s2;
+    yb[0] = th1_b;
+    yb[1] = th2_b;
+    yb[2] = fb[0] + om1_b;
+    yb[3] = fb[1] + om2_b;
+    ub[0] = w_b;
+  }
+  __device__ static __forceinline__ void post_vjp(const T (&)[S], const C&, T (&)[S]) {}
+  template <bool LEAN = false> __device__ static __forceinline__ void observe_vjp(const T (&)[S], const C& c, const T (&gob)[O], T (&r)[S]) {
+    observe_fields_vjp<T, Acrobot>(c, gob, r);
   }
   __device__ static __forceinline__ void post(T (&st)[S], const C&) {
     st[0] = wrap_angle(st[0]);
@@ -197,10 +339,23 @@ template <typename T> struct FluidTank {
   __device__ static __forceinline__ void prep(C& c) { c.den[0].init(c.P[0], c.fastdiv); }  // base_area
   __device__ static __forceinline__ void get_y(const T (&st)[S], T (&y)[NY]) { y[0] = st[0]; }
   __device__ static __forceinline__ void set_y(T (&st)[S], const T (&y)[NY]) { st[0] = y[0]; }
-  __device__ static __forceinline__ void f(const T (&y)[NY], const T (&u)[A], const C& c, const T (&)[S], T (&dy)[NY]) {
+  template <bool LEAN = false> __device__ static __forceinline__ void f(const T (&y)[NY], const T (&u)[A], const C& c, const T (&)[S], T (&dy)[NY]) {
     const T base_area = c.P[0], orifice_area = c.P[1], c_d = c.P[2], g = c.P[3];
     const T h = max_nan(y[0], T(0));
     dy[0] = c.den[0].div(u[0], c.fastdiv) - c_d * orifice_area / base_area * xsqrt(T(2) * g * h);
+  }
+  // d sqrt(2 g h) / d h = g / sqrt(2 g h) for h > 0, 0 for h <= 0 (the clamp's boundary included)
+  template <bool LEAN = false> __device__ static __forceinline__ void f_vjp(const T (&y)[NY], const T (&)[A], const C& c, const T (&)[S], const T (&fb)[NY],
+                                               T (&yb)[NY], T (&ub)[A], T&) {
+    const T base_area = c.P[0], orifice_area = c.P[1], c_d = c.P[2], g = c.P[3];
+    const bool wet = y[0] > T(0);
+    const T root = xsqrt(T(2) * g * (wet ? y[0] : T(1)));
+    yb[0] = wet ? -(fb[0] * (c_d * orifice_area / base_area * (g / root))) : T(0);
+    ub[0] = c.den[0].div(fb[0], c.fastdiv);
+  }
+  __device__ static __forceinline__ void post_vjp(const T (&sv)[S], const C&, T (&r)[S]) { r[0] = (sv[0] > T(0)) ? r[0] : T(0); }
+  template <bool LEAN = false> __device__ static __forceinline__ void observe_vjp(const T (&)[S], const C& c, const T (&gob)[O], T (&r)[S]) {
+    observe_fields_vjp<T, FluidTank>(c, gob, r);
   }
   __device__ static __forceinline__ void post(T (&st)[S], const C&) { st[0] = max_nan(st[0], T(0)); }
   __device__ static __forceinline__ void observe(const T (&st)[S], const C& c, T (&ob)[O]) {
@@ -221,7 +376,7 @@ template <typename T> struct Pmsm {
   }
   __device__ static __forceinline__ void get_y(const T (&st)[S], T (&y)[NY]) { y[0] = st[3]; y[1] = st[4]; y[2] = st[2]; }
   __device__ static __forceinline__ void set_y(T (&st)[S], const T (&y)[NY]) { st[3] = y[0]; st[4] = y[1]; st[2] = y[2]; }
-  __device__ static __forceinline__ void f(const T (&y)[NY], const T (&u)[A], const C& c, const T (&st)[S], T (&dy)[NY]) {
+  template <bool LEAN = false> __device__ static __forceinline__ void f(const T (&y)[NY], const T (&u)[A], const C& c, const T (&st)[S], T (&dy)[NY]) {
     const T r_s = c.P[1], l_d = c.P[2], l_q = c.P[3], psi_p = c.P[4];
     const T omega_el = st[6];
     const InvDiv<T>* d[2] = {&c.den[0], &c.den[1]};  // / l_d, / l_q
@@ -232,6 +387,22 @@ template <typename T> struct Pmsm {
     dy[1] = q[1];
     dy[2] = omega_el;
   }
+  // wb += (df / d omega_el)^T fb: omega_el is a constant of the trajectory that every step reads
+  template <bool LEAN = false> __device__ static __forceinline__ void f_vjp(const T (&y)[NY], const T (&)[A], const C& c, const T (&st)[S], const T (&fb)[NY],
+                                               T (&yb)[NY], T (&ub)[A], T& wb) {
+    const T r_s = c.P[1], l_d = c.P[2], l_q = c.P[3], psi_p = c.P[4];
+    const T omega_el = st[6];
+    const InvDiv<T>* d[2] = {&c.den[0], &c.den[1]};  // / l_d, / l_q
+    const T num[2] = {fb[0], fb[1]};
+    T q[2];
+    div_all<2, T>(d, num, q, c.fastdiv);
+    yb[0] = -(r_s * q[0]) - omega_el * l_d * q[1];
+    yb[1] = omega_el * l_q * q[0] - r_s * q[1];
+    yb[2] = T(0);
+    ub[0] = q[0];
+    ub[1] = q[1];
+    wb = wb + (l_q * y[1] * q[0] - (l_d * y[0] + psi_p) * q[1] + fb[2]);
+  }
   // pmsm_env.py:365-375
   __device__ static __forceinline__ T torque(T i_d, T i_q, const C& c) {
     const T p = c.P[0], l_d = c.P[2], l_q = c.P[3], psi_p = c.P[4];
@@ -241,6 +412,25 @@ template <typename T> struct Pmsm {
   __device__ static __forceinline__ void post(T (&st)[S], const C& c) {
     st[2] = wrap_angle(st[2]);
     st[5] = torque(st[3], st[4], c);
+  }
+  // transpose of post at the saved row: the torque leaf is a function of the currents (its own incoming value is overwritten)
+  __device__ static __forceinline__ void post_vjp(const T (&sv)[S], const C& c, T (&r)[S]) {
+    const T p = c.P[0], l_d = c.P[2], l_q = c.P[3], psi_p = c.P[4];
+    r[3] = r[3] + r[5] * (T(1.5) * p * (l_d - l_q) * sv[4]);
+    r[4] = r[4] + r[5] * (T(1.5) * p * (psi_p + (l_d - l_q) * sv[3]));
+    r[5] = T(0);
+  }
+  // transpose of observe: [i_d, i_q, omega_el, torque, cos eps, sin eps, u_d_buffer, u_q_buffer]
+  template <bool LEAN = false> __device__ static __forceinline__ void observe_vjp(const T (&sv)[S], const C& c, const T (&gob)[O], T (&r)[S]) {
+    T sn, cs;
+    sincos_x<LEAN>(sv[2], sn, cs);
+    r[3] = r[3] + normalize_field_vjp(c, 3, gob[0]);
+    r[4] = r[4] + normalize_field_vjp(c, 4, gob[1]);
+    r[6] = r[6] + normalize_field_vjp(c, 6, gob[2]);
+    r[5] = r[5] + normalize_field_vjp(c, 5, gob[3]);
+    r[2] = r[2] + (gob[5] * cs - gob[4] * sn);
+    r[0] = r[0] + normalize_field_vjp(c, 0, gob[6]);
+    r[1] = r[1] + normalize_field_vjp(c, 1, gob[7]);
   }
   // pmsm_env.py:898-919: [i_d, i_q, omega_el, torque, cos eps, sin eps, u_d_buffer, u_q_buffer]
   template <class CC> __device__ static __forceinline__ void observe(const T (&st)[S], const CC& c, T (&ob)[O]) {
@@ -291,7 +481,7 @@ template <typename T> struct Pmsm {
   }
 
   // pmsm_env.py:594-616 constraint_denormalization with the angle `eps` as given
-  template <class CC>
+  template <bool LEAN = false, class CC>
   __device__ static __forceinline__ void constraint(const T (&a)[A], T eps, T omega_el, const CC& c, T (&uc)[2]) {
     const T u_dc = c.P[5];
     const T half_dc = u_dc / T(2);
@@ -303,7 +493,7 @@ template <typename T> struct Pmsm {
     adv = pymod_two_pi(adv);
     adv = adv + ((adv > K<T>::pi) ? T(-2) * K<T>::pi : T(0));
     T sn, cs;
-    sincos_t(adv, sn, cs);
+    sincos_x<LEAN>(adv, sn, cs);
     const T sm = -sn;  // T(-adv) = [[cos, sin(-adv)], [-sin(-adv), cos]]
     T al = cs * n_d + sm * n_q;
     T be = (-sm) * n_d + cs * n_q;
@@ -312,6 +502,66 @@ template <typename T> struct Pmsm {
     const T o_q = (-sn) * al + cs * be;
     uc[0] = o_d * half_dc;
     uc[1] = o_q * half_dc;
+  }
+  // Transpose of constraint (rotation -> hexagon clip -> rotation back) at (a, eps, omega_el): ab += (d uc / d a)^T ucb,
+  // eb += (d uc / d eps)^T ucb, wb += (d uc / d omega_el)^T ucb (through the predicted angle). The sector bits are piecewise
+  // constant (derivative 0); a clamp passes its cotangent strictly inside its bounds only.
+  template <bool LEAN = false, class CC>
+  __device__ static __forceinline__ void constraint_vjp(const T (&a)[A], T eps, T omega_el, const CC& c, const T (&ucb)[2],
+                                                        T (&ab)[A], T& eb, T& wb) {
+    const T u_dc = c.P[5];
+    const T half_dc = u_dc / T(2);
+    const T u_d = denormalize(a[0], c.amin[0], c.amax[0]);
+    const T u_q = denormalize(a[1], c.amin[1], c.amax[1]);
+    const T sc = T(1) / half_dc;
+    const T n_d = u_d * sc, n_q = u_q * sc;
+    T adv = eps + c.adv_coef * omega_el;
+    adv = pymod_two_pi(adv);
+    adv = adv + ((adv > K<T>::pi) ? T(-2) * K<T>::pi : T(0));
+    T sn, cs;
+    sincos_x<LEAN>(adv, sn, cs);
+    const T re = cs * n_d - sn * n_q;
+    const T im = sn * n_d + cs * n_q;
+    // hex_clip with its intermediates
+    const T t = T(1.7320508075688772) * re;
+    const bool i0 = im >= T(0);
+    const bool i1 = (-im - t) >= T(0);
+    const bool i2 = (t - im) >= T(0);
+    const T q = T(0.8660254037844386f);
+    const T b0 = i0 ? T(1) : T(0), b1 = i1 ? T(1) : T(0), b2 = i2 ? T(1) : T(0);
+    const T d = b2 - b1;
+    const T ri = q * d;
+    const T neg = (T(1) - b0) * ((b1 > b2) ? b1 : b2);
+    const T rr = (T(1) - T(0.5f) * xabs(d)) * (T(1) - T(2) * neg);
+    const T tr0 = re * rr - im * ri;
+    const T ti0 = re * ri + im * rr;
+    const T lim_re = T(2.0 / 3.0);
+    const T lim_im = T(2.0 / 3.0) * xsqrt(T(3));
+    const T tr = min_nan(max_nan(tr0, -lim_re), lim_re);
+    const T ti = min_nan(max_nan(ti0, T(0)), lim_im);
+    const T al = tr * rr + ti * ri;
+    const T be = ti * rr - tr * ri;
+    // reverse: uc = (cs al + sn be, -sn al + cs be) * half_dc
+    const T od_b = ucb[0] * half_dc, oq_b = ucb[1] * half_dc;
+    const T al_b = cs * od_b - sn * oq_b;
+    const T be_b = sn * od_b + cs * oq_b;
+    T cs_b = od_b * al + oq_b * be;
+    T sn_b = od_b * be - oq_b * al;
+    T tr_b = al_b * rr - be_b * ri;
+    T ti_b = al_b * ri + be_b * rr;
+    tr_b = (tr0 > -lim_re && tr0 < lim_re) ? tr_b : T(0);
+    ti_b = (ti0 > T(0) && ti0 < lim_im) ? ti_b : T(0);
+    const T re_b = tr_b * rr + ti_b * ri;
+    const T im_b = ti_b * rr - tr_b * ri;
+    const T nd_b = cs * re_b + sn * im_b;
+    const T nq_b = cs * im_b - sn * re_b;
+    cs_b = cs_b + re_b * n_d + im_b * n_q;
+    sn_b = sn_b + im_b * n_d - re_b * n_q;
+    const T adv_b = sn_b * cs - cs_b * sn;
+    eb = eb + adv_b;
+    wb = wb + adv_b * c.adv_coef;
+    ab[0] = ab[0] + nd_b * sc * (T(0.5) * (c.amax[0] - c.amin[0]));
+    ab[1] = ab[1] + nq_b * sc * (T(0.5) * (c.amax[1] - c.amin[1]));
   }
 };
 

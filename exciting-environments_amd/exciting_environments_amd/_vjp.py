@@ -1,0 +1,187 @@
+"""Reverse mode of `vmap_sim_ahead`: the explicit vector-Jacobian product `vmap_sim_ahead_vjp` (one persistent launch of
+sim_ahead_vjp_kernel through `excenv_sim_ahead_vjp`, include/excenv.h) and the `torch.autograd.Function` that `vmap_sim_ahead`
+goes through when `env.differentiable` is set and something asks for a gradient. Mixed into `CoreEnvironment` (core_env.py).
+
+The kernel reads the state trajectory the forward call returned (its rows are the per-step checkpoints) and lane-major
+cotangents. A cotangent that is not laid out lane-major — autograd hands such tensors back after a `select` or a `sum` (an
+expanded scalar, a zero-filled row-major block) — is copied into a lane-major buffer first: one strided pass over the tensor (its cost
+next to the launch's: DESIGN.md §4.9)."""
+from __future__ import annotations
+
+import ctypes
+from dataclasses import replace
+
+import torch
+from torch.autograd.function import once_differentiable
+
+from . import _native
+
+_EM, _LM = _native.LAYOUT_ENV_MAJOR, _native.LAYOUT_LANE_MAJOR
+
+
+def _leaf_list(x, fields):
+    """State / PhysicalState pytree or a sequence -> list of leaves (None where absent)."""
+    if x is None:
+        return None
+    x = getattr(x, "physical_state", x)
+    if isinstance(x, (list, tuple)):
+        assert len(x) == len(fields), f"expected {len(fields)} state leaves"
+        return list(x)
+    return [getattr(x, n, None) for n in fields]
+
+
+class _SimAhead(torch.autograd.Function):
+    """vmap_sim_ahead with a graph behind its outputs: (actions, initial physical-state leaves) -> (observations, state
+    trajectory leaves, last-state leaves). Saves the actions and the state trajectory; backward is one reverse launch."""
+
+    @staticmethod
+    def forward(ctx, env, init_state, obs_stepsize, action_stepsize, actions, *leaves):
+        ctx.set_materialize_grads(False)
+        S = env.physical_state_dim
+        st = replace(init_state, physical_state=env.PhysicalState(*[t.detach() for t in leaves]))
+        B = env.batch_size
+        obs, st_views, last, N = env._run_sim_ahead(st, actions.detach(), env.env_properties, obs_stepsize, action_stepsize, B)
+        # aliases of the launch's outputs: the pooled sets' own tensor objects never carry a grad_fn, and a live graph keeps the
+        # set's storage busy through them (the pools hand a set out again only when nothing refers to its memory)
+        outs = [obs.detach()] + [t.detach() for t in st_views] + [t.detach() for t in last]
+        ctx.env, ctx.steps, ctx.N = env, (obs_stepsize, action_stepsize), N
+        ctx.save_for_backward(actions, *outs[1:1 + S])
+        return tuple(outs)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_obs, *g):
+        env = ctx.env
+        S = env.physical_state_dim
+        actions, *traj = ctx.saved_tensors
+        g_states, g_last = list(g[:S]), list(g[S:])
+        ga, gs = env._sim_ahead_vjp_launch(traj, actions, ctx.steps[0], ctx.steps[1], g_obs,
+                                           g_states if any(t is not None for t in g_states) else None,
+                                           g_last if any(t is not None for t in g_last) else None)
+        need = ctx.needs_input_grad
+        return (None, None, None, None, ga if need[4] else None) + tuple(t if n else None for t, n in zip(gs, need[5:]))
+
+
+class TrajectoryVjpMixin:
+    @property
+    def differentiable(self) -> bool:
+        """False (default): vmap_sim_ahead returns plain tensors, exactly as without this property. True: when grad mode is on
+        and the actions or a leaf of the initial physical state require grad, the call records one autograd node whose backward
+        is the reverse-mode kernel (the state trajectory is always produced then; not combinable with out=,
+        return_rew_trunc_term=True or anything vmap_sim_ahead_vjp rejects)."""
+        return getattr(self, "_differentiable", False)
+
+    @differentiable.setter
+    def differentiable(self, value):
+        self._differentiable = bool(value)
+
+    def _vjp_unsupported(self):
+        """The reason this environment's configuration has no reverse mode, or None."""
+        if self.sim_ahead_semantics not in ("ahead", "step"):
+            return f"sim_ahead_semantics={self.sim_ahead_semantics!r} has no reverse mode (use 'ahead' or 'step')"
+        if self.traj_layout != "lane_major":
+            return f"traj_layout={self.traj_layout!r} has no reverse mode (the 'env_major' and 'tiled' layouts are forward only)"
+        if getattr(self.env_properties, "saturated", False):
+            return "the saturated PMSM has no reverse mode"
+        if self._props_for(self.env_properties, self.batch_size)[1]:
+            return "per-environment property arrays have no reverse mode (broadcast properties only)"
+        return None
+
+    def _wants_grad(self, init_state, actions):
+        if not (self.differentiable and torch.is_grad_enabled()):
+            return False
+        if isinstance(actions, torch.Tensor) and actions.requires_grad:
+            return True
+        return any(isinstance(t, torch.Tensor) and t.requires_grad
+                   for t in (getattr(init_state.physical_state, n) for n in self.STATE_FIELDS))
+
+    def _sim_ahead_differentiable(self, init_state, actions, obs_stepsize, action_stepsize):
+        why = self._vjp_unsupported()
+        if why is None and not self.store_state_trajectory:
+            why = "store_state_trajectory=False: the reverse pass reads the state trajectory"
+        if why is None and actions.ndim != 3:
+            why = "tiled actions have no reverse mode"
+        if why is not None:
+            raise ValueError(f"vmap_sim_ahead(differentiable): {why}")
+        B, S = self.batch_size, self.physical_state_dim
+        leaves = [self._t(getattr(init_state.physical_state, n), (B,)) for n in self.STATE_FIELDS]
+        if actions.device != self.device or actions.dtype != self.dtype:
+            actions = actions.to(device=self.device, dtype=self.dtype)
+        outs = _SimAhead.apply(self, init_state, obs_stepsize, action_stepsize, actions, *leaves)
+        obs, st_views, last = outs[0], outs[1:1 + S], outs[1 + S:]
+        N = st_views[0].shape[1] - 1
+        states = self._traj_state(init_state, st_views, (B,), N)
+        last_state = self.State(self.PhysicalState(*last), init_state.PRNGKey, self._additions((B,), True), init_state.reference)
+        return obs, states, last_state
+
+    # ------------------------------------------------------------------ the explicit form
+    def vmap_sim_ahead_vjp(self, states, actions, obs_stepsize, action_stepsize, grad_observations=None, grad_states=None,
+                           grad_last_state=None):
+        """Vector-Jacobian product of `vmap_sim_ahead(init_state, actions, obs_stepsize, action_stepsize)`.
+        states: the `states` that call returned (its rows are the checkpoints the reverse pass recomputes from);
+        grad_observations [B, N+1, obs_dim], grad_states (a State / PhysicalState pytree or a sequence of [B, N+1] leaves, None where
+        absent), grad_last_state (likewise, [B] leaves): the cotangents, any of them may be None.
+        Returns (grad_actions [B, K, A] — a view of lane-major [K, A, B] memory —, PhysicalState of [B] gradients w.r.t. the
+        initial physical state). Derivatives of clamps / clips are 0 on the boundary, of sign 0."""
+        why = self._vjp_unsupported()
+        if why is not None:
+            raise ValueError(f"vmap_sim_ahead_vjp: {why}")
+        traj = _leaf_list(states, self.STATE_FIELDS)
+        ga, gs = self._sim_ahead_vjp_launch(traj, torch.as_tensor(actions), obs_stepsize, action_stepsize, grad_observations,
+                                            _leaf_list(grad_states, self.STATE_FIELDS), _leaf_list(grad_last_state, self.STATE_FIELDS))
+        return ga, self.PhysicalState(*gs)
+
+    def _lane_major(self, g, shape, strides):
+        """g as a tensor of `shape` whose memory is lane-major (`strides`): itself when it is, else a copy."""
+        g = g if (g.device == self.device and g.dtype == self.dtype) else g.to(device=self.device, dtype=self.dtype)
+        assert tuple(g.shape) == shape, f"cotangent of shape {tuple(g.shape)}, expected {shape}"
+        if tuple(g.stride()) == strides and g.data_ptr() % 16 == 0:
+            return g
+        buf = torch.empty_strided(shape, strides, dtype=self.dtype, device=self.device)
+        buf.copy_(g)
+        return buf
+
+    def _sim_ahead_vjp_launch(self, traj, actions, obs_stepsize, action_stepsize, g_obs, g_states, g_last):
+        B, S, A, OW = self.batch_size, self.physical_state_dim, self.action_dim, self._obs_dim()
+        dt, dev = self.dtype, self.device
+        assert actions.ndim == 3 and actions.shape[0] == B and actions.shape[2] == A, \
+            "The actions need to have three dimensions: (batch_size, n_action_steps, action_dim)"
+        K = actions.shape[1]
+        sub = self._n_substeps(K, obs_stepsize, action_stepsize)
+        rows = K * sub + 1
+        sB = B or 1
+        if actions.device != dev or actions.dtype != dt:
+            actions = actions.to(device=dev, dtype=dt)
+        actions = actions.detach()
+        if K > 0 and B > 0 and tuple(actions.stride()) == (1, A * B, B):
+            a_layout = _LM
+        else:
+            actions, a_layout = actions.contiguous(), _EM
+        for t in traj:
+            if not (isinstance(t, torch.Tensor) and tuple(t.shape) == (B, rows) and (tuple(t.stride()) == (1, sB) or B == 0)
+                    and t.dtype is dt and t.is_cuda):
+                raise ValueError("vmap_sim_ahead_vjp: `states` must be the lane-major state trajectory a vmap_sim_ahead call with "
+                                 "these actions and step sizes returned (the 'env_major' and 'tiled' layouts have no reverse mode)")
+        if g_obs is not None:
+            g_obs = self._lane_major(g_obs, (B, rows, OW), (1, OW * sB, sB))
+        if g_states is not None:
+            g_states = [None if g is None else self._lane_major(g, (B, rows), (1, sB)) for g in g_states]
+        if g_last is not None:
+            g_last = [None if g is None else self._lane_major(g, (B,), (1,)) for g in g_last]
+        props, keep = self._props_for(self.env_properties, B)
+        control = None
+        if self.control_state:
+            control = _native.Control()
+            control.n_control = len(self.control_state)
+        grad_actions = torch.empty((K, A, B), dtype=dt, device=dev)
+        grad_in = torch.empty((S, (B + 3) // 4 * 4), dtype=dt, device=dev)  # every leaf 16-byte aligned
+        gs = [grad_in[j, :B] for j in range(S)]
+        ws_bytes = _native.lib().excenv_sim_ahead_vjp_workspace_bytes(self.ENV_ID, _native.dtype_id(dt), B, K, a_layout)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes > 0 else None
+        opt_ptrs = lambda ts: None if ts is None else (ctypes.c_void_p * S)(*[None if t is None else t.data_ptr() for t in ts])
+        _native._launch("excenv_sim_ahead_vjp", grad_actions, "vmap_sim_ahead_vjp", self.ENV_ID, self._solver.id,
+                        _native.dtype_id(dt), B, K, sub, ctypes.byref(props), _native._ref(control), float(obs_stepsize),
+                        float(self.tau), actions.data_ptr() if K > 0 else None, a_layout, _native._ptrs(traj), _native._ptr(g_obs),
+                        opt_ptrs(g_states), opt_ptrs(g_last), grad_actions.data_ptr() if K > 0 else None, _native._ptrs(gs),
+                        self._semantics_id, _native._ptr(ws), ws_bytes, _native._ref(self.launch_opts))
+        return grad_actions.permute(2, 0, 1), gs

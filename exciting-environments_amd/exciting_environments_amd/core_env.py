@@ -28,6 +28,7 @@ from ._native import cuda_get_device as _cuda_get_device, cuda_is_capturing as _
 from . import random as _random
 from ._placement import StepSlotPool, TrajectoryPlacement
 from ._trajectory import TrajectoryLaunchMixin
+from ._vjp import TrajectoryVjpMixin
 from .solvers import Euler, _Solver
 from .tree import tree_structure
 
@@ -42,7 +43,7 @@ def _is_scalar(x) -> bool:
     return _is_array(x) and x.ndim == 0
 
 
-class CoreEnvironment(TrajectoryLaunchMixin, ABC):
+class CoreEnvironment(TrajectoryLaunchMixin, TrajectoryVjpMixin, ABC):
     """Core structure of the provided environments (reference core_env.py:15-57).
 
     The simulated systems are physical state-space models dx/dt = f(x(t), u(t)); outputs are
@@ -116,6 +117,8 @@ class CoreEnvironment(TrajectoryLaunchMixin, ABC):
         self.store_state_trajectory = True
         # per-call launch options (excenv_launch_opts_t); None = library defaults. Tuning experiments only.
         self.launch_opts = None
+        # True: vmap_sim_ahead records an autograd node when a gradient is asked for (_vjp.py); False: plain tensors, as ever
+        self.differentiable = False
         self._packed_props = None
         self._packed_for = None
         self._flag_cache = {}
@@ -907,6 +910,11 @@ class CoreEnvironment(TrajectoryLaunchMixin, ABC):
             + f"{(self.batch_size, self.physical_state_dim)}, but {init_physical_state_shape} is given"
         )
         B = self.batch_size
+        if self._wants_grad(init_state, actions):  # env.differentiable and something requires grad: one autograd node (_vjp.py)
+            if out is not None or return_rew_trunc_term:
+                raise ValueError("vmap_sim_ahead: a differentiable call cannot be combined with out= or return_rew_trunc_term=True "
+                                 "(their outputs have no reverse mode); detach the inputs or set env.differentiable = False")
+            return self._sim_ahead_differentiable(init_state, actions, obs_stepsize, action_stepsize)
         gym_out = None
         if return_rew_trunc_term:
             if out is not None:

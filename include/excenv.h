@@ -260,6 +260,34 @@ int excenv_sim_ahead_ws(int env, int solver, int dtype, int64_t B, int64_t K, in
 int excenv_sim_ahead_fuses_actions(int env, int solver, int dtype, int64_t B, int64_t K, const excenv_props_t* props,
                                    int32_t n_control, int with_gym, int action_layout, int traj_layout, const void* actions,
                                    const excenv_launch_opts_t* opts);
+/* ---- reverse mode of excenv_sim_ahead (what jax.grad of the reference's vmap_sim_ahead gives; addition, same ABI version: a
+ * binder probes for the symbol). One persistent launch computes the vector-Jacobian product of a trajectory call from the state
+ * rows that call saved: it re-evaluates one step's stages per row and streams the rows from N down to 0.
+ *   control         : only n_control is read (the width of a grad_obs_traj row; the control columns' cotangents are skipped:
+ *                     those columns are constants of the trajectory)
+ *   actions         : the forward call's actions, EXCENV_LAYOUT_LANE_MAJOR, or EXCENV_LAYOUT_ENV_MAJOR with a workspace of
+ *                     excenv_sim_ahead_vjp_workspace_bytes (the library transposes them into it, excenv_transpose's kernel)
+ *   state_traj      : S pointers to the lane-major [N+1][B] state trajectories the forward call wrote
+ *   grad_obs_traj   : cotangent of obs_traj, lane-major [N+1][O + n_control][B], or NULL
+ *   grad_state_traj : NULL, or S pointers to cotangents of the state trajectories ([N+1][B]), each may be NULL
+ *   grad_last_state : NULL, or S pointers to cotangents of last_state ([B]), each may be NULL
+ *   grad_actions    : out, lane-major [K][A][B]
+ *   grad_state_in   : out, S pointers to [B]: the gradient w.r.t. every leaf of the initial physical state
+ *   semantics       : EXCENV_SEM_AHEAD or EXCENV_SEM_STEP, the forward call's
+ * opts->envs_per_lane: 0 = the forward's batch rule, 1 or 16 / sizeof(dtype) = forced (the wide form needs B % that == 0 and
+ * 16-byte aligned arrays). Derivatives of clamps / clips are 0 on the boundary, of sign 0, of the tank's sqrt term 0 at h <= 0.
+ * Not supported, rejected before any launch: the saturated PMSM (pmsm_lut), EXCENV_SEM_AHEAD_ACCUMULATED_T, the tiled layout and
+ * per-environment property arrays (EXCENV_EUNSUPPORTED); gradients w.r.t. properties do not exist.
+ * excenv_last_launch() then reports "sim_ahead_vjp_kernel (V=1|V=2|V=4)". */
+int64_t excenv_sim_ahead_vjp_workspace_bytes(int env, int dtype, int64_t B, int64_t K, int action_layout);
+int excenv_sim_ahead_vjp(int env, int solver, int dtype, int64_t B, int64_t K, int32_t substeps,
+                         const excenv_props_t* props, const excenv_control_t* control, double obs_stepsize,
+                         double env_tau, const void* actions, int action_layout, const void* const* state_traj,
+                         const void* grad_obs_traj, const void* const* grad_state_traj,
+                         const void* const* grad_last_state, void* grad_actions, void* const* grad_state_in,
+                         int semantics, void* workspace, int64_t workspace_bytes, const excenv_launch_opts_t* opts,
+                         void* stream);
+
 /* out[n][m] = in[m][n] for a row-major M x N matrix of the given dtype (the conversion kernel used above). */
 int excenv_transpose(int dtype, int64_t M, int64_t N, const void* in, void* out, void* stream);
 

@@ -1,0 +1,374 @@
+"""Reverse mode of vmap_sim_ahead on the GPU (sim_ahead_vjp_kernel) against the float64 torch twin (tests/helpers_vjp.py, validated
+in tests/test_vjp_twin.py) and, independently of the twin, against central differences of the fp64 forward kernel.
+
+Bounds.
+1. fp64 kernel vs twin: 1e-8 of each gradient tensor's largest magnitude (both sides evaluate the same expressions in fp64).
+2. Directional finite difference, h = 1e-5 in normalised action units: 1e-6 of the batch's largest directional derivative
+   (truncation ~h^2 = 1e-10, round-off ~eps / h = 1e-11 of the loss).
+3. fp32 kernel vs twin: the tolerance cannot be derived, so it is tied to parent-commit code — the relative distance of the fp32
+   FORWARD observations from the twin's fp64 forward on the same inputs (the floor); the fp32 gradients must lie within 32 x that
+   floor, relative to each tensor's largest magnitude (the adjoint re-evaluates every step's stages in fp32 and applies as many
+   transposed-Jacobian products again). Environments the twin's fp64 forward sees within helpers_vjp.KINK_MARGIN of a kink are
+   excluded from this check only, at most 2 % per case. Every case prints its floor, bound and measured distance; the figures
+   measured on an MI355X are in DESIGN.md §5.
+"""
+import numpy as np
+import pytest
+import torch
+
+from conftest import ENV_NAMES
+from helpers import ANGLE_OBS, make_env, spec_of, to_state
+from helpers_vjp import KINK_CAP, KINK_MARGIN, Twin, leaves, vjp_inputs
+
+pytestmark = pytest.mark.gpu
+
+CASES = [(e, None) for e in ENV_NAMES if e != "pmsm"] + [("pmsm", 0), ("pmsm", 1)]
+SOLVERS = ["euler", "rk4", "tsit5"]
+B0, K0 = 256, 40
+
+
+def case_spec(env_name, deadtime):
+    spec = spec_of(env_name)
+    if deadtime is not None:
+        spec["params"]["deadtime"] = deadtime
+    return spec
+
+
+def dev(x, env):
+    return torch.as_tensor(np.asarray(x), dtype=env.dtype, device=env.device)
+
+
+class GpuRun:
+    """One forward launch on the GPU and the reverse launches over its state trajectory."""
+
+    def __init__(self, env_name, spec, dtype, solver, semantics, st_np, acts_np, sub=1, control_state=None, envs_per_lane=0,
+                 lane_major_actions=True, reference=None, step=None):
+        from exciting_environments_amd import _native
+
+        self.env, _, _, _ = make_env(env_name, st_np[0].shape[0], dtype, solver, spec=spec, control_state=control_state)
+        env = self.env
+        env.sim_ahead_semantics = semantics
+        if envs_per_lane:
+            env.launch_opts = _native.launch_opts(envs_per_lane=envs_per_lane)
+        self.tau, self.sub = (spec["tau"] if step is None else step), sub  # the solver's step (obs_stepsize)
+        K = acts_np.shape[1]
+        if lane_major_actions:
+            self.actions = env.new_actions_buffer(K)
+            self.actions.copy_(dev(acts_np, env))
+        else:
+            self.actions = dev(acts_np, env).contiguous()
+        self.state = to_state(env, st_np, reference=reference)
+        self.obs, self.states, self.last = env.vmap_sim_ahead(self.state, self.actions, self.tau, self.tau * sub)
+
+    def vjp(self, g_obs=None, g_states=None, g_last=None):
+        from exciting_environments_amd import _native
+
+        env = self.env
+        ga, gs = env.vmap_sim_ahead_vjp(
+            self.states, self.actions, self.tau, self.tau * self.sub,
+            None if g_obs is None else dev(g_obs, env),
+            None if g_states is None else [None if g is None else dev(g, env) for g in g_states],
+            None if g_last is None else [None if g is None else dev(g, env) for g in g_last])
+        self.launch = _native.last_launch()
+        torch.cuda.synchronize()
+        return ga.cpu().numpy().astype(np.float64), [getattr(gs, n).cpu().numpy().astype(np.float64) for n in env.STATE_FIELDS]
+
+
+def cotangents(rng, B, rows, OW, S):
+    return rng.normal(size=(B, rows, OW)), [rng.normal(size=(B, rows)) for _ in range(S)], [rng.normal(size=B) for _ in range(S)]
+
+
+def twin_grads(twin, st_np, acts_np, tau, sub, groups, O):
+    """Twin gradients for several cotangent groups over one forward graph -> list of (grad_actions, [grad leaves]), kink distance,
+    forward observations"""
+    st = leaves(st_np, True)
+    act = torch.tensor(np.asarray(acts_np, dtype=np.float64), requires_grad=True)
+    obs, states, last = twin.sim_ahead(st, act, tau, sub)
+    out = []
+    for g_obs, g_states, g_last in groups:
+        loss = torch.zeros((), dtype=torch.float64)
+        if g_obs is not None:
+            loss = loss + (obs * torch.as_tensor(g_obs[..., :O])).sum()
+        if g_states is not None:
+            loss = loss + sum((s * torch.as_tensor(g)).sum() for s, g in zip(states, g_states))
+        if g_last is not None:
+            loss = loss + sum((s * torch.as_tensor(g)).sum() for s, g in zip(last, g_last))
+        gr = torch.autograd.grad(loss, [act] + st, allow_unused=True, retain_graph=True)
+        z = lambda g, like: np.zeros(tuple(like.shape)) if g is None else g.numpy()
+        out.append((z(gr[0], act), [z(g, s) for g, s in zip(gr[1:], st)]))
+    return out, twin.kink_distance(), obs.detach().numpy()
+
+
+def rel_dist(got, want, keep=None):
+    """max |got - want| over the kept environments, relative to the tensor's largest magnitude"""
+    if keep is not None:
+        got, want = got[keep], want[keep]
+    scale = float(np.max(np.abs(want))) if want.size else 0.0
+    return float(np.max(np.abs(got - want))) / scale if scale > 0 else float(np.max(np.abs(got), initial=0.0))
+
+
+def obs_floor(got, want, env_name, keep=None):
+    """Relative distance of forward observations (the fp32 floor): over the kept environments only, normalised wrapped angles
+    compared on the circle of period 2 (an fp32 / fp64 wrap flip at +-pi is no distance)"""
+    got, want = np.array(got, dtype=np.float64), np.array(want, dtype=np.float64)
+    if keep is not None:
+        got, want = got[keep], want[keep]
+    d = np.abs(got - want)
+    for c in ANGLE_OBS.get(env_name, []):
+        d[..., c] = np.minimum(d[..., c], np.abs(2.0 - d[..., c]))
+    return float(d.max()) / float(np.max(np.abs(want)))
+
+
+# ---------------------------------------------------------------------------------------------------------------- 1
+@pytest.mark.parametrize("semantics", ["ahead", "step"])
+@pytest.mark.parametrize("solver", SOLVERS)
+@pytest.mark.parametrize("env_name,deadtime", CASES)
+def test_fp64_kernel_matches_the_twin(env_name, deadtime, solver, semantics):
+    spec = case_spec(env_name, deadtime)
+    st, acts = vjp_inputs(env_name, spec, B0, K0, seed=11)
+    run = GpuRun(env_name, spec, torch.float64, solver, semantics, st, acts)
+    S, O = len(st), run.obs.shape[-1]
+    g_obs, g_states, g_last = cotangents(np.random.default_rng(5), B0, K0 + 1, O, S)
+    groups = [(g_obs, g_states, g_last), (g_obs, None, None), (None, g_states, None), (None, None, g_last)]
+    want, _, _ = twin_grads(Twin(env_name, spec, solver, semantics), st, acts, spec["tau"], 1, groups, O)
+    for grp, (wa, ws) in zip(groups, want):
+        ga, gs = run.vjp(*grp)
+        assert run.launch.startswith("sim_ahead_vjp_kernel")
+        d = [rel_dist(ga, wa)] + [rel_dist(g, w) for g, w in zip(gs, ws)]
+        print(f"{env_name} dead={deadtime} {solver} {semantics} groups={[g is not None for g in grp]}: rel dist {max(d):.3e}")
+        assert max(d) <= 1e-8
+
+
+@pytest.mark.parametrize("env_name", [e for e in ENV_NAMES if e != "pmsm"])
+def test_fp64_kernel_matches_the_twin_with_substeps(env_name):
+    spec = spec_of(env_name)
+    K, sub = 10, 4
+    st, acts = vjp_inputs(env_name, spec, B0, K, seed=12)
+    for solver, semantics in (("rk4", "ahead"), ("euler", "step")):
+        run = GpuRun(env_name, spec, torch.float64, solver, semantics, st, acts, sub=sub)
+        S, O = len(st), run.obs.shape[-1]
+        grp = cotangents(np.random.default_rng(6), B0, K * sub + 1, O, S)
+        (wa, ws), = twin_grads(Twin(env_name, spec, solver, semantics), st, acts, spec["tau"], sub, [grp], O)[0]
+        ga, gs = run.vjp(*grp)
+        d = [rel_dist(ga, wa)] + [rel_dist(g, w) for g, w in zip(gs, ws)]
+        print(f"{env_name} {solver} {semantics} substeps={sub}: rel dist {max(d):.3e}")
+        assert max(d) <= 1e-8
+
+
+def test_fp64_kernel_matches_the_twin_with_control_state():
+    """control_state columns are constants of the trajectory: their cotangent columns are skipped"""
+    env_name, solver, semantics = "pendulum", "tsit5", "ahead"
+    spec = spec_of(env_name)
+    st, acts = vjp_inputs(env_name, spec, B0, K0, seed=13)
+    run = GpuRun(env_name, spec, torch.float64, solver, semantics, st, acts, control_state=["theta"],
+                 reference={"theta": np.full(B0, 0.3)})
+    S, OW = len(st), run.obs.shape[-1]
+    assert OW == 3
+    grp = cotangents(np.random.default_rng(7), B0, K0 + 1, OW, S)
+    (wa, ws), = twin_grads(Twin(env_name, spec, solver, semantics), st, acts, spec["tau"], 1, [grp], 2)[0]
+    ga, gs = run.vjp(*grp)
+    assert max([rel_dist(ga, wa)] + [rel_dist(g, w) for g, w in zip(gs, ws)]) <= 1e-8
+
+
+# ---------------------------------------------------------------------------------------------------------------- 2
+@pytest.mark.parametrize("semantics", ["ahead", "step"])
+@pytest.mark.parametrize("solver", SOLVERS)
+@pytest.mark.parametrize("env_name,deadtime", CASES)
+def test_directional_finite_difference_of_the_fp64_forward(env_name, deadtime, solver, semantics):
+    """<grad_actions, delta> per environment against (L(a + h delta) - L(a - h delta)) / 2h of two forward launches.
+    The tank steps by 100 tau here: at tau = 1e-4 s its level moves by 1e-7 of itself per step, the derivative w.r.t. the actions is
+    7e-5 of the loss, and the round-off of the two forward launches (eps / h of the LOSS, accumulated over the steps) is 2e-6 of
+    such a derivative — measured 1.7e-6 ... 2.7e-6 for the six tank cases, while the same gradients agree with the twin to 1e-8.
+    With a step that lets the level move the difference quotient resolves the derivative like it does for the other models."""
+    spec = case_spec(env_name, deadtime)
+    step = 100 * spec["tau"] if env_name == "fluid_tank" else None
+    st, acts = vjp_inputs(env_name, spec, B0, K0, seed=21)
+    rng = np.random.default_rng(8)
+    delta = rng.normal(size=acts.shape)
+    h = 1e-5
+    run = GpuRun(env_name, spec, torch.float64, solver, semantics, st, acts, step=step)
+    S, O = len(st), run.obs.shape[-1]
+    w_obs, w_states, w_last = cotangents(rng, B0, K0 + 1, O, S)
+
+    def loss(r):  # per environment
+        o = r.obs.cpu().numpy()
+        L = (o * w_obs).sum(axis=(1, 2))
+        for n, ws, wl in zip(r.env.STATE_FIELDS, w_states, w_last):
+            L = L + (getattr(r.states.physical_state, n).cpu().numpy() * ws).sum(axis=1)
+            L = L + getattr(r.last.physical_state, n).cpu().numpy() * wl
+        return L
+
+    ga, _ = run.vjp(w_obs, w_states, w_last)
+    lp = loss(GpuRun(env_name, spec, torch.float64, solver, semantics, st, acts + h * delta, step=step))
+    lm = loss(GpuRun(env_name, spec, torch.float64, solver, semantics, st, acts - h * delta, step=step))
+    fd = (lp - lm) / (2 * h)
+    dd = (ga * delta).sum(axis=(1, 2))
+    scale = float(np.max(np.abs(fd)))
+    err = float(np.max(np.abs(dd - fd))) / scale
+    print(f"{env_name} dead={deadtime} {solver} {semantics}: directional derivative rel err {err:.3e} (scale {scale:.3e})")
+    if step is not None:  # the tank at its own tau as well: reported next to the asserted figure (see the docstring)
+        run0 = GpuRun(env_name, spec, torch.float64, solver, semantics, st, acts)
+        ga0, _ = run0.vjp(w_obs, w_states, w_last)
+        fd0 = (loss(GpuRun(env_name, spec, torch.float64, solver, semantics, st, acts + h * delta))
+               - loss(GpuRun(env_name, spec, torch.float64, solver, semantics, st, acts - h * delta))) / (2 * h)
+        err0 = float(np.max(np.abs((ga0 * delta).sum(axis=(1, 2)) - fd0))) / float(np.max(np.abs(fd0)))
+        print(f"{env_name} {solver} {semantics} at tau: directional derivative rel err {err0:.3e} (difference quotient's round-off)")
+    assert err <= 1e-6
+
+
+# ---------------------------------------------------------------------------------------------------------------- 3, 4
+@pytest.mark.parametrize("semantics", ["ahead", "step"])
+@pytest.mark.parametrize("solver", SOLVERS)
+@pytest.mark.parametrize("env_name,deadtime", CASES)
+def test_fp32_kernel_within_32x_the_forward_floor(env_name, deadtime, solver, semantics):
+    spec = case_spec(env_name, deadtime)
+    st, acts = vjp_inputs(env_name, spec, B0, K0, seed=11)
+    st32, acts32 = [v.astype(np.float32) for v in st], acts.astype(np.float32)
+    st, acts = [v.astype(np.float64) for v in st32], acts32.astype(np.float64)  # the same values on both sides
+    run = GpuRun(env_name, spec, torch.float32, solver, semantics, st32, acts32)
+    S, O = len(st), run.obs.shape[-1]
+    grp = cotangents(np.random.default_rng(5), B0, K0 + 1, O, S)
+    grp = (grp[0].astype(np.float32).astype(np.float64), [g.astype(np.float32).astype(np.float64) for g in grp[1]],
+           [g.astype(np.float32).astype(np.float64) for g in grp[2]])
+    (want,), kd, obs64 = twin_grads(Twin(env_name, spec, solver, semantics), st, acts, spec["tau"], 1, [grp], O)
+    keep = np.ones(B0, dtype=bool) if kd is None else (kd.numpy() >= KINK_MARGIN)
+    excluded = 1.0 - keep.mean()
+    assert excluded <= KINK_CAP
+    floor = obs_floor(run.obs.cpu().numpy(), obs64, env_name, keep)  # parent-commit code: the fp32 forward
+    bound = 32 * floor
+    ga, gs = run.vjp(*grp)
+    d = [rel_dist(ga, want[0], keep)] + [rel_dist(g, w, keep) for g, w in zip(gs, want[1])]
+    print(f"{env_name} dead={deadtime} {solver} {semantics}: forward floor {floor:.3e}, bound {bound:.3e}, gradients {max(d):.3e}, "
+          f"excluded {excluded:.4f}")
+    assert max(d) <= bound
+
+
+# ---------------------------------------------------------------------------------------------------------------- 5
+@pytest.mark.parametrize("env_name,solver,dtype,wide", [("pendulum", "tsit5", torch.float32, 4), ("pmsm", "euler", torch.float32, 4),
+                                                        ("cartpole", "euler", torch.float64, 2), ("fluid_tank", "rk4", torch.float64, 2)])
+def test_same_bits_across_forms(env_name, solver, dtype, wide):
+    spec = spec_of(env_name)
+    B, K = 1024, 16
+    npdt = np.float32 if dtype is torch.float32 else np.float64
+    st, acts = vjp_inputs(env_name, spec, B, K, seed=31, np_dtype=npdt)
+    S = len(st)
+    got = {}
+    for form, lane_major in ((1, True), (wide, True), (wide, False)):
+        run = GpuRun(env_name, spec, dtype, solver, "ahead", st, acts, envs_per_lane=form, lane_major_actions=lane_major)
+        grp = cotangents(np.random.default_rng(9), B, K + 1, run.obs.shape[-1], S)
+        ga, gs = run.vjp(*grp)
+        assert run.launch == f"sim_ahead_vjp_kernel (V={form})"
+        got[(form, lane_major)] = np.concatenate([ga.ravel()] + gs)
+    ref = got[(1, True)]
+    assert np.isfinite(ref).all() and np.abs(ref).max() > 0
+    for key, val in got.items():
+        assert np.array_equal(ref, val), key
+
+
+# ---------------------------------------------------------------------------------------------------------------- 6
+def test_large_batch_takes_the_wide_form_and_matches_the_twin_on_a_slice():
+    env_name, solver, semantics = "pmsm", "euler", "ahead"
+    spec = spec_of(env_name)
+    B, K, NS = 1 << 19, 8, 512
+    st, acts = vjp_inputs(env_name, spec, B, K, seed=41, np_dtype=np.float32)
+    run = GpuRun(env_name, spec, torch.float32, solver, semantics, st, acts)
+    S, O = len(st), run.obs.shape[-1]
+    rng = np.random.default_rng(10)
+    g_last = [rng.normal(size=B).astype(np.float32) for _ in range(S)]
+    g_obs = rng.normal(size=(B, K + 1, O)).astype(np.float32)
+    ga, gs = run.vjp(g_obs, None, g_last)
+    assert run.launch == "sim_ahead_vjp_kernel (V=4)"
+    sl = slice(B // 2, B // 2 + NS)
+    grp = (g_obs[sl].astype(np.float64), None, [g[sl].astype(np.float64) for g in g_last])
+    (want,), kd, obs64 = twin_grads(Twin(env_name, spec, solver, semantics), [v[sl].astype(np.float64) for v in st],
+                                    acts[sl].astype(np.float64), spec["tau"], 1, [grp], O)
+    keep = kd.numpy() >= KINK_MARGIN
+    assert 1.0 - keep.mean() <= KINK_CAP
+    floor = obs_floor(run.obs[sl].cpu().numpy(), obs64, env_name, keep)
+    d = [rel_dist(ga[sl], want[0], keep)] + [rel_dist(g[sl], w, keep) for g, w in zip(gs, want[1])]
+    print(f"pmsm euler fp32 B=2^19: forward floor {floor:.3e}, bound {32 * floor:.3e}, gradients {max(d):.3e}")
+    assert max(d) <= 32 * floor
+
+
+@pytest.mark.parametrize("env_name,lane_major", [("pmsm", True), ("pendulum", False)])
+def test_autograd_path_equals_the_explicit_call(env_name, lane_major):
+    spec = spec_of(env_name)
+    B, K = 2048, 12
+    st, acts = vjp_inputs(env_name, spec, B, K, seed=51, np_dtype=np.float32)
+    env, _, _, _ = make_env(env_name, B, torch.float32, "rk4", spec=spec)
+    assert env.differentiable is False
+    state = to_state(env, st)
+    if lane_major:
+        actions = env.new_actions_buffer(K)
+        actions.copy_(dev(acts, env))
+    else:
+        actions = dev(acts, env).contiguous()
+    actions.requires_grad_(True)
+    # differentiable = False: tensors without a graph, as ever
+    obs, states, last = env.vmap_sim_ahead(state, actions, spec["tau"], spec["tau"])
+    assert obs.grad_fn is None and not obs.requires_grad
+    assert all(getattr(states.physical_state, n).grad_fn is None for n in env.STATE_FIELDS)
+    env.differentiable = True
+    leaf = env.STATE_FIELDS[-1]
+    getattr(state.physical_state, leaf).requires_grad_(True)
+    obs, states, last = env.vmap_sim_ahead(state, actions, spec["tau"], spec["tau"])
+    assert obs.grad_fn is not None
+    loss = obs[:, -1].pow(2).sum()
+    loss.backward()
+    assert tuple(actions.grad.shape) == (B, K, env.action_dim)
+    g_obs = torch.zeros_like(obs.detach())
+    g_obs[:, -1] = 2 * obs.detach()[:, -1]
+    ga, gs = env.vmap_sim_ahead_vjp(states, actions.detach(), spec["tau"], spec["tau"], grad_observations=g_obs)
+    torch.cuda.synchronize()
+    assert torch.equal(actions.grad, ga)
+    assert torch.equal(getattr(state.physical_state, leaf).grad, getattr(gs, leaf))
+    assert float(actions.grad.abs().max()) > 0
+    with pytest.raises(ValueError, match="out="):
+        env.vmap_sim_ahead(state, actions, spec["tau"], spec["tau"], out=(obs, states, last))
+    with pytest.raises(ValueError, match="return_rew_trunc_term"):
+        env.vmap_sim_ahead(state, actions, spec["tau"], spec["tau"], return_rew_trunc_term=True)
+    env.sim_ahead_semantics = "ahead_accumulated_t"
+    with pytest.raises(ValueError, match="ahead_accumulated_t"):
+        env.vmap_sim_ahead(state, actions, spec["tau"], spec["tau"])
+
+
+def test_a_pooled_set_saved_by_a_live_graph_is_not_handed_out_again():
+    """Output sets of 1 GiB and more are pooled: a set is written again two calls later when nothing refers to it. The state
+    trajectory an autograd node saved must keep its set busy although no Python reference to the outputs is left."""
+    spec = spec_of("pmsm")
+    B, K = 1 << 20, 20  # (8 + 7) columns x 21 rows x 4 bytes x 2^20 = 1.26 GiB
+    st, acts = vjp_inputs("pmsm", spec, B, K, seed=61, np_dtype=np.float32)
+    env, _, _, _ = make_env("pmsm", B, torch.float32, "euler", spec=spec)
+    env.differentiable = True
+    state = to_state(env, st)
+    actions = env.new_actions_buffer(K)
+    actions.copy_(dev(acts, env))
+    actions.requires_grad_(True)
+    obs, states, last = env.vmap_sim_ahead(state, actions, spec["tau"], spec["tau"])
+    saved_ptr = states.physical_state.i_d.data_ptr()
+    g_last = [torch.ones(B, device=env.device) for _ in env.STATE_FIELDS]
+    want, _ = env.vmap_sim_ahead_vjp(states, actions.detach(), spec["tau"], spec["tau"], grad_last_state=g_last)
+    want = want.clone()
+    loss = sum(getattr(last.physical_state, n).sum() for n in env.STATE_FIELDS)
+    del obs, states, last
+    plain = actions.detach()
+    ptrs = []
+    for _ in range(4):  # without the graph the first set would be written again by the third call
+        o, s, l = env.vmap_sim_ahead(state, plain, spec["tau"] * 0.5, spec["tau"] * 0.5)
+        ptrs.append(s.physical_state.i_d.data_ptr())
+        del o, s, l
+    assert saved_ptr not in ptrs
+    loss.backward()
+    torch.cuda.synchronize()
+    assert torch.equal(actions.grad, want)
+    # the control: once the graph is gone the set is dead and comes back
+    from exciting_environments_amd import _placement
+
+    del loss
+    if env.trajectory_pool and _placement.liveness_available():
+        again = []
+        for _ in range(4):
+            o, s, l = env.vmap_sim_ahead(state, plain, spec["tau"] * 0.5, spec["tau"] * 0.5)
+            again.append(s.physical_state.i_d.data_ptr())
+            del o, s, l
+        assert saved_ptr in again
