@@ -298,6 +298,14 @@ int64_t excenv_sim_ahead_vjp_workspace_bytes(int env, int dtype, int64_t B, int6
   return vjp_workspace_bytes(t->A, dtype == EXCENV_F64 ? 8 : 4, B, K, action_layout);
 }
 
+int64_t excenv_sim_ahead_vjp_workspace_bytes_for(int env, int solver, int dtype, int64_t B, int64_t K, int32_t substeps,
+                                                 int semantics, int action_layout) {
+  const EnvVTable* t = table_public(env);
+  if (!t || B < 0 || K < 0 || substeps < 1) return -1;
+  const int elem = dtype == EXCENV_F64 ? 8 : 4;
+  return vjp_workspace_bytes(t->A, elem, B, K, action_layout) + vjp_raw_rows_bytes(env, solver, semantics, elem, B, K, substeps);
+}
+
 int excenv_sim_ahead_vjp(int env, int solver, int dtype, int64_t B, int64_t K, int32_t substeps,
                          const excenv_props_t* props, const excenv_control_t* control, double obs_stepsize,
                          double env_tau, const void* actions, int action_layout, const void* const* state_traj,
@@ -339,6 +347,16 @@ int excenv_sim_ahead_vjp(int env, int solver, int dtype, int64_t B, int64_t K, i
     }
     k_actions = workspace;
   }
+  void* raw_rows = nullptr;
+  if (B > 0 && K > 0 && vjp_needs_raw_rows(env, solver, semantics)) {
+    const int64_t head = transposed ? vjp_workspace_bytes(t->A, elem, B, K, action_layout) : 0;
+    const int64_t need = head + vjp_raw_rows_bytes(env, solver, semantics, elem, B, K, substeps);
+    if (!workspace || workspace_bytes < need) {
+      set_error("%s: this model, solver and semantics need a workspace of %lld bytes (excenv_sim_ahead_vjp_workspace_bytes_for)", fn, (long long)need);
+      return EXCENV_EINVAL;
+    }
+    raw_rows = (char*)workspace + head;
+  }
   // the wide form: whole lanes and 16-byte accesses everywhere
   bool wide_ok = (B % (16 / elem)) == 0 && align_of(k_actions) >= 16 && align_of(grad_actions) >= 16 && align_of(grad_obs_traj) >= 16;
   for (int j = 0; j < t->S; ++j) {
@@ -356,7 +374,7 @@ int excenv_sim_ahead_vjp(int env, int solver, int dtype, int64_t B, int64_t K, i
     if (int rc = launch_transpose(dtype, B, K * t->A, actions, workspace, (hipStream_t)stream)) { set_error("%s: action transpose failed", fn); return rc; }
   }
   const VjpCall vc{solver, dtype, B, K, substeps, nc, props, obs_stepsize, env_tau, semantics, k_actions, state_traj, grad_obs_traj,
-                   grad_state_traj, grad_last_state, grad_actions, grad_state_in, V, stream};
+                   grad_state_traj, grad_last_state, grad_actions, grad_state_in, V, raw_rows, stream};
   return t->sim_vjp(vc);
 }
 

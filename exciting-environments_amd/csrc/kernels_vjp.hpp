@@ -511,6 +511,37 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(2)))
   for (int j = 0; j < S; ++j) store_v<T, V>((ka.g_state_in[j] + blk0) + lane, sb[j]);
 }
 
+// The raw levels of the tank under EXCENV_SEM_AHEAD (vjp.hpp vjp_needs_raw_rows): the forward's own steps (env_advance_raw) again,
+// one environment per lane, from the saved rows into raw[N + 1][B]. A saved row above 0 IS the raw level (the clamp is the identity
+// there) and restarts the recurrence; a saved 0 stands for a raw level at or below 0, which the recurrence carries on from the last
+// wet row. Row 0 is taken as saved: an initial level below 0 — outside the model's range — is read as 0. One pass of the forward's
+// arithmetic without its stores of observations: cheaper than the forward launch it follows.
+template <class M, typename T, int SOLVER>
+__global__ void __launch_bounds__(BLOCK) vjp_raw_rows_kernel(const VjpArgs<T, M> ka, T* __restrict__ raw) {
+  static_assert(M::S == 1 && M::A == 1 && !M::IS_PMSM, "the tank: one level, one action");
+  const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+  Ctx<T, M> c;
+  load_ctx<false>(c, ka.kp, 0, ka.dt, ka.env_tau, ka.adv_coef);
+  if (i >= ka.B) return;
+  const int64_t B = ka.B, K = ka.K, N = ka.K * ka.substeps;
+  AheadAux<T> aux{};
+  T st[1] = {ka.straj[0][i]};
+  int64_t k = 0;
+  int32_t sub = 0;
+  for (int64_t n = 0;; ++n) {
+    const T saved = ka.straj[0][n * B + i];
+    st[0] = (saved > T(0)) ? saved : st[0];
+    raw[n * B + i] = st[0];
+    if (n == N) break;
+    const bool last_sub = sub == ka.substeps - 1;
+    const int64_t k1 = (last_sub && k < K - 1) ? k + 1 : k;  // the row of the c_i == 1 stages
+    const T a[1] = {ka.actions[k * B + i]}, a1[1] = {ka.actions[k1 * B + i]};
+    env_advance_raw<M, SOLVER>(st, a, a1, k, k1, c, aux);
+    sub = last_sub ? 0 : sub + 1;
+    k = last_sub ? k + 1 : k;
+  }
+}
+
 // Packs VjpArgs and launches the instantiation the call names (vjp.hpp vjp_instantiated): every other combination is an error
 template <class M, typename T> static int launch_vjp(const VjpCall& vc) {
   VjpArgs<T, M> ka;
@@ -547,6 +578,15 @@ template <class M, typename T> static int launch_vjp(const VjpCall& vc) {
   if (vc.B == 0) return EXCENV_OK;
   const dim3 grid((unsigned)((vc.B / vc.V + BLOCK - 1) / BLOCK)), block(BLOCK);
   const hipStream_t stream = (hipStream_t)vc.stream;
+  if constexpr (M::ID == EXCENV_FLUID_TANK) {
+    if (vc.raw_rows != nullptr) {  // the reverse kernel reads the raw levels in place of the saved (clamped) ones
+      const dim3 grid1((unsigned)((vc.B + BLOCK - 1) / BLOCK));
+      if (vc.solver == EXCENV_RK4) hipLaunchKernelGGL((vjp_raw_rows_kernel<M, T, EXCENV_RK4>), grid1, block, 0, stream, ka, (T*)vc.raw_rows);
+      else hipLaunchKernelGGL((vjp_raw_rows_kernel<M, T, EXCENV_TSIT5>), grid1, block, 0, stream, ka, (T*)vc.raw_rows);
+      if (int rc = check_launch("excenv_sim_ahead_vjp (raw rows)")) return rc;
+      ka.straj[0] = (const T*)vc.raw_rows;
+    }
+  }
   const bool launched = vjp_instantiated(vc.semantics, M::ID, (int)sizeof(T), vc.solver, M::HAS_LUT, vc.V) && with_solver(vc.solver, [&](auto solver) {
     return with_flag(ahead, [&](auto ah) {
       return with_const<1, 2, 4>(vc.V, [&](auto v) {

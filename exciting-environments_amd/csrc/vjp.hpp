@@ -21,6 +21,7 @@ struct VjpCall {
   void* grad_actions;                   // [K][A][B]
   void* const* grad_state_in;           // S x [B]
   int V;                                // environments per lane (vjp_envs_per_lane)
+  void* raw_rows;                       // [N + 1][B] workspace where vjp_needs_raw_rows, else nullptr
   void* stream;                         // hipStream_t
 };
 
@@ -54,6 +55,18 @@ constexpr int vjp_envs_per_lane(int env, int solver, int64_t B, int elem, int fo
 // Workspace of a call whose actions are row-major [B][K][A]: their lane-major copy
 constexpr int64_t vjp_workspace_bytes(int A, int elem, int64_t B, int64_t K, int action_layout) {
   return action_layout == EXCENV_LAYOUT_ENV_MAJOR ? align_up(elem * K * A * B) : 0;
+}
+
+// The saved rows are the reverse pass's checkpoints, and under EXCENV_SEM_AHEAD they are post-processed copies of the raw state the
+// forward carries. For the tank that copy loses what an RK step starts from: a level that ran below 0 is saved as 0, and a stage
+// state built from 0 is not the one built from the raw level (it may be wet where the raw one is dry). Those calls re-simulate the
+// raw levels first (vjp_raw_rows_kernel) into a second part of the workspace, behind the transposed actions. Euler's only stage
+// state is the row itself, which f reads as max(h, 0): nothing to restore. No other model's post-processing changes a Jacobian.
+constexpr bool vjp_needs_raw_rows(int env, int solver, int semantics) {
+  return env == EXCENV_FLUID_TANK && solver != EXCENV_EULER && semantics == EXCENV_SEM_AHEAD;
+}
+constexpr int64_t vjp_raw_rows_bytes(int env, int solver, int semantics, int elem, int64_t B, int64_t K, int32_t substeps) {
+  return vjp_needs_raw_rows(env, solver, semantics) ? align_up(elem * (K * substeps + 1) * B) : 0;
 }
 
 constexpr const char* vjp_name(int V) {

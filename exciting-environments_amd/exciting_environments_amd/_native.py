@@ -98,6 +98,7 @@ PROTOTYPES = {
     "excenv_sim_ahead_ws": (_ci, _AHEAD + [_vp, _i64, _vp, _vp]),
     "excenv_sim_ahead_fuses_actions": (_ci, [_ci, _ci, _ci, _i64, _i64, _vp, _i32, _ci, _ci, _ci, _vp, _vp]),
     "excenv_sim_ahead_vjp_workspace_bytes": (_i64, [_ci, _ci, _i64, _i64, _ci]),
+    "excenv_sim_ahead_vjp_workspace_bytes_for": (_i64, [_ci, _ci, _ci, _i64, _i64, _i32, _ci, _ci]),
     # ... props, control, obs_stepsize, env_tau, actions, layout, state_traj, grad_obs, grad_states, grad_last, grad_actions,
     # grad_state_in, semantics, workspace, workspace_bytes, opts, stream
     "excenv_sim_ahead_vjp": (_ci, [_ci, _ci, _ci, _i64, _i64, _i32, _vp, _vp, _cd, _cd, _vp, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _ci,

@@ -176,7 +176,10 @@ class TrajectoryVjpMixin:
         grad_actions = torch.empty((K, A, B), dtype=dt, device=dev)
         grad_in = torch.empty((S, (B + 3) // 4 * 4), dtype=dt, device=dev)  # every leaf 16-byte aligned
         gs = [grad_in[j, :B] for j in range(S)]
-        ws_bytes = _native.lib().excenv_sim_ahead_vjp_workspace_bytes(self.ENV_ID, _native.dtype_id(dt), B, K, a_layout)
+        # the transposed copy of row-major actions and, where the saved rows do not determine the steps' starting points (the tank
+        # under "ahead" with an RK solver), the raw levels a pass in front of the launch restores
+        ws_bytes = _native.lib().excenv_sim_ahead_vjp_workspace_bytes_for(self.ENV_ID, self._solver.id, _native.dtype_id(dt), B, K, sub,
+                                                                          self._semantics_id, a_layout)
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes > 0 else None
         opt_ptrs = lambda ts: None if ts is None else (ctypes.c_void_p * S)(*[None if t is None else t.data_ptr() for t in ts])
         _native._launch("excenv_sim_ahead_vjp", grad_actions, "vmap_sim_ahead_vjp", self.ENV_ID, self._solver.id,

@@ -278,8 +278,15 @@ int excenv_sim_ahead_fuses_actions(int env, int solver, int dtype, int64_t B, in
  * 16-byte aligned arrays). Derivatives of clamps / clips are 0 on the boundary, of sign 0, of the tank's sqrt term 0 at h <= 0.
  * Not supported, rejected before any launch: the saturated PMSM (pmsm_lut), EXCENV_SEM_AHEAD_ACCUMULATED_T, the tiled layout and
  * per-environment property arrays (EXCENV_EUNSUPPORTED); gradients w.r.t. properties do not exist.
- * excenv_last_launch() then reports "sim_ahead_vjp_kernel (V=1|V=2|V=4)". */
+ * excenv_last_launch() then reports "sim_ahead_vjp_kernel (V=1|V=2|V=4)".
+ * Workspace: excenv_sim_ahead_vjp_workspace_bytes_for (addition) is the size for a given call — the transposed actions and,
+ * for the tank under EXCENV_SEM_AHEAD with RK4 / Tsit5, the raw levels [N+1][B] a pass in front of the reverse launch restores
+ * (the saved rows hold max(h, 0); an RK stage state built from a clamped row is not the one the forward built from the raw level).
+ * excenv_sim_ahead_vjp_workspace_bytes is the transposed actions' part alone: enough for every other call, and a call that needs
+ * more fails with EXCENV_EINVAL and the size. */
 int64_t excenv_sim_ahead_vjp_workspace_bytes(int env, int dtype, int64_t B, int64_t K, int action_layout);
+int64_t excenv_sim_ahead_vjp_workspace_bytes_for(int env, int solver, int dtype, int64_t B, int64_t K, int32_t substeps,
+                                                 int semantics, int action_layout);
 int excenv_sim_ahead_vjp(int env, int solver, int dtype, int64_t B, int64_t K, int32_t substeps,
                          const excenv_props_t* props, const excenv_control_t* control, double obs_stepsize,
                          double env_tau, const void* actions, int action_layout, const void* const* state_traj,

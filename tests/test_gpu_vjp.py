@@ -17,106 +17,13 @@ import pytest
 import torch
 
 from conftest import ENV_NAMES
-from helpers import ANGLE_OBS, make_env, spec_of, to_state
-from helpers_vjp import KINK_CAP, KINK_MARGIN, Twin, leaves, vjp_inputs
+from helpers import make_env, spec_of, to_state
+from helpers_vjp import (CASES, KINK_CAP, KINK_MARGIN, SOLVERS, GpuRun, Twin, case_spec, cotangents, dev, obs_floor, rel_dist,
+                         twin_grads, vjp_inputs)
 
 pytestmark = pytest.mark.gpu
 
-CASES = [(e, None) for e in ENV_NAMES if e != "pmsm"] + [("pmsm", 0), ("pmsm", 1)]
-SOLVERS = ["euler", "rk4", "tsit5"]
 B0, K0 = 256, 40
-
-
-def case_spec(env_name, deadtime):
-    spec = spec_of(env_name)
-    if deadtime is not None:
-        spec["params"]["deadtime"] = deadtime
-    return spec
-
-
-def dev(x, env):
-    return torch.as_tensor(np.asarray(x), dtype=env.dtype, device=env.device)
-
-
-class GpuRun:
-    """One forward launch on the GPU and the reverse launches over its state trajectory."""
-
-    def __init__(self, env_name, spec, dtype, solver, semantics, st_np, acts_np, sub=1, control_state=None, envs_per_lane=0,
-                 lane_major_actions=True, reference=None, step=None):
-        from exciting_environments_amd import _native
-
-        self.env, _, _, _ = make_env(env_name, st_np[0].shape[0], dtype, solver, spec=spec, control_state=control_state)
-        env = self.env
-        env.sim_ahead_semantics = semantics
-        if envs_per_lane:
-            env.launch_opts = _native.launch_opts(envs_per_lane=envs_per_lane)
-        self.tau, self.sub = (spec["tau"] if step is None else step), sub  # the solver's step (obs_stepsize)
-        K = acts_np.shape[1]
-        if lane_major_actions:
-            self.actions = env.new_actions_buffer(K)
-            self.actions.copy_(dev(acts_np, env))
-        else:
-            self.actions = dev(acts_np, env).contiguous()
-        self.state = to_state(env, st_np, reference=reference)
-        self.obs, self.states, self.last = env.vmap_sim_ahead(self.state, self.actions, self.tau, self.tau * sub)
-
-    def vjp(self, g_obs=None, g_states=None, g_last=None):
-        from exciting_environments_amd import _native
-
-        env = self.env
-        ga, gs = env.vmap_sim_ahead_vjp(
-            self.states, self.actions, self.tau, self.tau * self.sub,
-            None if g_obs is None else dev(g_obs, env),
-            None if g_states is None else [None if g is None else dev(g, env) for g in g_states],
-            None if g_last is None else [None if g is None else dev(g, env) for g in g_last])
-        self.launch = _native.last_launch()
-        torch.cuda.synchronize()
-        return ga.cpu().numpy().astype(np.float64), [getattr(gs, n).cpu().numpy().astype(np.float64) for n in env.STATE_FIELDS]
-
-
-def cotangents(rng, B, rows, OW, S):
-    return rng.normal(size=(B, rows, OW)), [rng.normal(size=(B, rows)) for _ in range(S)], [rng.normal(size=B) for _ in range(S)]
-
-
-def twin_grads(twin, st_np, acts_np, tau, sub, groups, O):
-    """Twin gradients for several cotangent groups over one forward graph -> list of (grad_actions, [grad leaves]), kink distance,
-    forward observations"""
-    st = leaves(st_np, True)
-    act = torch.tensor(np.asarray(acts_np, dtype=np.float64), requires_grad=True)
-    obs, states, last = twin.sim_ahead(st, act, tau, sub)
-    out = []
-    for g_obs, g_states, g_last in groups:
-        loss = torch.zeros((), dtype=torch.float64)
-        if g_obs is not None:
-            loss = loss + (obs * torch.as_tensor(g_obs[..., :O])).sum()
-        if g_states is not None:
-            loss = loss + sum((s * torch.as_tensor(g)).sum() for s, g in zip(states, g_states))
-        if g_last is not None:
-            loss = loss + sum((s * torch.as_tensor(g)).sum() for s, g in zip(last, g_last))
-        gr = torch.autograd.grad(loss, [act] + st, allow_unused=True, retain_graph=True)
-        z = lambda g, like: np.zeros(tuple(like.shape)) if g is None else g.numpy()
-        out.append((z(gr[0], act), [z(g, s) for g, s in zip(gr[1:], st)]))
-    return out, twin.kink_distance(), obs.detach().numpy()
-
-
-def rel_dist(got, want, keep=None):
-    """max |got - want| over the kept environments, relative to the tensor's largest magnitude"""
-    if keep is not None:
-        got, want = got[keep], want[keep]
-    scale = float(np.max(np.abs(want))) if want.size else 0.0
-    return float(np.max(np.abs(got - want))) / scale if scale > 0 else float(np.max(np.abs(got), initial=0.0))
-
-
-def obs_floor(got, want, env_name, keep=None):
-    """Relative distance of forward observations (the fp32 floor): over the kept environments only, normalised wrapped angles
-    compared on the circle of period 2 (an fp32 / fp64 wrap flip at +-pi is no distance)"""
-    got, want = np.array(got, dtype=np.float64), np.array(want, dtype=np.float64)
-    if keep is not None:
-        got, want = got[keep], want[keep]
-    d = np.abs(got - want)
-    for c in ANGLE_OBS.get(env_name, []):
-        d[..., c] = np.minimum(d[..., c], np.abs(2.0 - d[..., c]))
-    return float(d.max()) / float(np.max(np.abs(want)))
 
 
 # ---------------------------------------------------------------------------------------------------------------- 1

@@ -35,6 +35,18 @@ def test_header_declares_and_library_exports_the_vjp_entry_points():
     assert wb(5, 0, 1000, 10, _native.LAYOUT_LANE_MAJOR) == 0
     assert wb(5, 0, 1000, 10, _native.LAYOUT_ENV_MAJOR) == (4 * 10 * 2 * 1000 + 255) // 256 * 256
     assert wb(17, 0, 1000, 10, 0) == -1
+    # the size for a given call: the tank under "ahead" with an RK solver adds the raw levels [K * substeps + 1][B]
+    assert re.search(r"\bint64_t\s+excenv_sim_ahead_vjp_workspace_bytes_for\s*\(", hdr)
+    wbf = _native.lib().excenv_sim_ahead_vjp_workspace_bytes_for
+    up = lambda n: (n + 255) // 256 * 256
+    lm, em = _native.LAYOUT_LANE_MAJOR, _native.LAYOUT_ENV_MAJOR
+    assert wbf(4, 1, _native.F64, 1000, 10, 3, _native.SEM_AHEAD, lm) == up(8 * 31 * 1000)
+    assert wbf(4, 2, _native.F32, 1000, 10, 1, _native.SEM_AHEAD, em) == up(4 * 10 * 1000) + up(4 * 11 * 1000)
+    assert wbf(4, 0, _native.F64, 1000, 10, 3, _native.SEM_AHEAD, lm) == 0  # Euler: the stage state is the saved row
+    assert wbf(4, 1, _native.F64, 1000, 10, 3, _native.SEM_STEP, lm) == 0   # "step" carries the post-processed state
+    for env in (0, 1, 2, 3, 5):
+        assert wbf(env, 2, _native.F32, 1000, 10, 1, _native.SEM_AHEAD, em) == wb(env, _native.F32, 1000, 10, em)
+    assert wbf(17, 0, 0, 1000, 10, 1, _native.SEM_AHEAD, lm) == -1 and wbf(4, 1, 0, 1000, 10, 0, _native.SEM_AHEAD, lm) == -1
 
 
 def _call(env=0, solver=0, dtype=0, B=4, K=3, sub=1, props=None, semantics=_native.SEM_AHEAD, layout=_native.LAYOUT_LANE_MAJOR,
@@ -78,6 +90,10 @@ def test_unsupported_combinations_are_rejected_before_any_launch():
     assert _call(sub=0)[0] == EINVAL
     rc, msg = _call(layout=_native.LAYOUT_ENV_MAJOR)  # row-major actions without their workspace
     assert rc == EINVAL and b"workspace" in msg
+    rc, msg = _call(env=4, solver=1)  # the tank, RK4, "ahead": the raw levels need their workspace
+    assert rc == EINVAL and b"excenv_sim_ahead_vjp_workspace_bytes_for" in msg
+    rc, msg = _call(env=4, solver=1, ws=vp(256), ws_bytes=255)
+    assert rc == EINVAL and b"256 bytes" in msg  # B = 4, K = 3, fp32: 4 * 4 * 4 = 64 -> 256
     rc, msg = _call(opts=_native.LaunchOpts(2, 0, 0, 0))  # fp32: the forms are 1 and 4 environments per lane
     assert rc == EINVAL and b"envs_per_lane" in msg
     rc, msg = _call(env=3, solver=2, opts=_native.LaunchOpts(4, 0, 0, 0))  # acrobot Tsit5 has the one-environment form only
@@ -163,6 +179,11 @@ static_assert(vjp_instantiated(EXCENV_SEM_AHEAD, EXCENV_PMSM, 4, EXCENV_EULER, f
 static_assert(!vjp_instantiated(EXCENV_SEM_AHEAD, EXCENV_PMSM, 4, EXCENV_EULER, true, 1), "saturated PMSM");
 static_assert(!vjp_instantiated(EXCENV_SEM_AHEAD_ACCUMULATED_T, EXCENV_PENDULUM, 4, EXCENV_EULER, false, 1), "");
 static_assert(vjp_workspace_bytes(2, 4, 1000, 10, EXCENV_LAYOUT_LANE_MAJOR) == 0, "");
+static_assert(vjp_needs_raw_rows(EXCENV_FLUID_TANK, EXCENV_TSIT5, EXCENV_SEM_AHEAD), "");
+static_assert(!vjp_needs_raw_rows(EXCENV_FLUID_TANK, EXCENV_EULER, EXCENV_SEM_AHEAD), "");
+static_assert(!vjp_needs_raw_rows(EXCENV_FLUID_TANK, EXCENV_RK4, EXCENV_SEM_STEP), "");
+static_assert(!vjp_needs_raw_rows(EXCENV_PENDULUM, EXCENV_RK4, EXCENV_SEM_AHEAD), "");
+static_assert(vjp_raw_rows_bytes(EXCENV_FLUID_TANK, EXCENV_RK4, EXCENV_SEM_AHEAD, 8, 1000, 10, 3) == 248064, "31 rows, 256-byte units");
 int main() { return 0; }
 ''')
     subprocess.run([cxx, "-std=c++17", "-I", os.path.join(ROOT, "exciting-environments_amd", "csrc"), "-fsyntax-only", str(src)], check=True)
