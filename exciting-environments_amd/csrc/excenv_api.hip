@@ -22,6 +22,7 @@ void set_error(const char* fmt, ...) {
 }
 
 int launch_transpose(int dtype, int64_t M, int64_t N, const void* in, void* out, hipStream_t stream);
+int launch_param_sum(int dtype, int64_t B, int n, const void* const* per_env, void* out, void* workspace, hipStream_t stream);
 
 EnvVTable vtable_pendulum();
 EnvVTable vtable_msd();
@@ -306,14 +307,16 @@ int64_t excenv_sim_ahead_vjp_workspace_bytes_for(int env, int solver, int dtype,
   return vjp_workspace_bytes(t->A, elem, B, K, action_layout) + vjp_raw_rows_bytes(env, solver, semantics, elem, B, K, substeps);
 }
 
-int excenv_sim_ahead_vjp(int env, int solver, int dtype, int64_t B, int64_t K, int32_t substeps,
-                         const excenv_props_t* props, const excenv_control_t* control, double obs_stepsize,
-                         double env_tau, const void* actions, int action_layout, const void* const* state_traj,
-                         const void* grad_obs_traj, const void* const* grad_state_traj,
-                         const void* const* grad_last_state, void* grad_actions, void* const* grad_state_in,
-                         int semantics, void* workspace, int64_t workspace_bytes, const excenv_launch_opts_t* opts,
-                         void* stream) {
-  const char* fn = "excenv_sim_ahead_vjp";
+}  // extern "C"
+
+// excenv_sim_ahead_vjp (grad_params == nullptr, pgrad false) and excenv_sim_ahead_vjp_params: one validation, one launch
+static int sim_ahead_vjp_call(const char* fn, bool pgrad, int env, int solver, int dtype, int64_t B, int64_t K, int32_t substeps,
+                              const excenv_props_t* props, const excenv_control_t* control, double obs_stepsize,
+                              double env_tau, const void* actions, int action_layout, const void* const* state_traj,
+                              const void* grad_obs_traj, const void* const* grad_state_traj,
+                              const void* const* grad_last_state, void* grad_actions, void* const* grad_state_in,
+                              int semantics, void* workspace, int64_t workspace_bytes, const excenv_launch_opts_t* opts,
+                              void* stream, void* const* grad_params) {
   if (int rc = check_common(fn, env, solver, dtype, B)) return rc;
   if (K < 0 || substeps < 1) { set_error("%s: bad K=%lld or substeps=%d", fn, (long long)K, substeps); return EXCENV_EINVAL; }
   if (semantics == EXCENV_SEM_AHEAD_ACCUMULATED_T) {
@@ -326,6 +329,19 @@ int excenv_sim_ahead_vjp(int env, int solver, int dtype, int64_t B, int64_t K, i
   if (!props || !state_traj || !grad_state_in || ((!actions || !grad_actions) && K > 0)) { set_error("%s: NULL argument", fn); return EXCENV_ENULL; }
   if (props->pmsm_lut) { set_error("%s: the saturated PMSM (pmsm_lut) has no reverse mode", fn); return EXCENV_EUNSUPPORTED; }
   const EnvVTable* t = table_public(env);
+  bool params_aligned = true;
+  if (pgrad) {
+    if (!grad_params) { set_error("%s: NULL argument", fn); return EXCENV_ENULL; }
+    bool any = false;
+    for (int j = 0; j < EXCENV_MAX_STATIC; ++j) {
+      if (!grad_params[j]) continue;
+      if (j >= t->P) { set_error("%s: grad_params[%d]: this model has %d static parameters", fn, j, t->P); return EXCENV_EINVAL; }
+      if (!vjp_param_differentiable(env, j)) { set_error("%s: grad_params[%d]: static parameter %d is an integer leaf and has no gradient", fn, j, j); return EXCENV_EINVAL; }
+      any = true;
+      params_aligned = params_aligned && align_of(grad_params[j]) >= 16;
+    }
+    if (!any) { set_error("%s: every entry of grad_params is NULL (excenv_sim_ahead_vjp is the call without parameter gradients)", fn); return EXCENV_EINVAL; }
+  }
   const int nc = control ? control->n_control : 0;
   if (nc < 0 || nc > EXCENV_MAX_CONTROL) { set_error("%s: bad n_control %d", fn, nc); return EXCENV_EINVAL; }
   if (int rc = check_opts(fn, opts)) return rc;
@@ -358,14 +374,14 @@ int excenv_sim_ahead_vjp(int env, int solver, int dtype, int64_t B, int64_t K, i
     raw_rows = (char*)workspace + head;
   }
   // the wide form: whole lanes and 16-byte accesses everywhere
-  bool wide_ok = (B % (16 / elem)) == 0 && align_of(k_actions) >= 16 && align_of(grad_actions) >= 16 && align_of(grad_obs_traj) >= 16;
+  bool wide_ok = params_aligned && (B % (16 / elem)) == 0 && align_of(k_actions) >= 16 && align_of(grad_actions) >= 16 && align_of(grad_obs_traj) >= 16;
   for (int j = 0; j < t->S; ++j) {
     if (!state_traj[j] || !grad_state_in[j]) { set_error("%s: state pointer %d is NULL", fn, j); return EXCENV_ENULL; }
     wide_ok = wide_ok && align_of(state_traj[j]) >= 16 && align_of(grad_state_in[j]) >= 16 &&
               (!grad_state_traj || align_of(grad_state_traj[j]) >= 16) && (!grad_last_state || align_of(grad_last_state[j]) >= 16);
   }
-  const int V = vjp_envs_per_lane(env, solver, B, elem, opts->envs_per_lane, wide_ok);
-  if (V == 0 || !vjp_instantiated(semantics, env, elem, solver, false, V)) {
+  const int V = vjp_envs_per_lane(env, solver, B, elem, opts->envs_per_lane, wide_ok, pgrad);
+  if (V == 0 || !vjp_instantiated(semantics, env, elem, solver, false, V, pgrad)) {
     set_error("%s: opts.envs_per_lane = %d is not available (1, or %d where the model and solver have that form, with batch_size %% %d == 0 and 16-byte aligned arrays)", fn,
               opts->envs_per_lane, 16 / elem, 16 / elem);
     return EXCENV_EINVAL;
@@ -374,8 +390,63 @@ int excenv_sim_ahead_vjp(int env, int solver, int dtype, int64_t B, int64_t K, i
     if (int rc = launch_transpose(dtype, B, K * t->A, actions, workspace, (hipStream_t)stream)) { set_error("%s: action transpose failed", fn); return rc; }
   }
   const VjpCall vc{solver, dtype, B, K, substeps, nc, props, obs_stepsize, env_tau, semantics, k_actions, state_traj, grad_obs_traj,
-                   grad_state_traj, grad_last_state, grad_actions, grad_state_in, V, raw_rows, stream};
+                   grad_state_traj, grad_last_state, grad_actions, grad_state_in, V, raw_rows, stream, pgrad ? grad_params : nullptr};
   return t->sim_vjp(vc);
+}
+
+extern "C" {
+
+int excenv_sim_ahead_vjp(int env, int solver, int dtype, int64_t B, int64_t K, int32_t substeps,
+                         const excenv_props_t* props, const excenv_control_t* control, double obs_stepsize,
+                         double env_tau, const void* actions, int action_layout, const void* const* state_traj,
+                         const void* grad_obs_traj, const void* const* grad_state_traj,
+                         const void* const* grad_last_state, void* grad_actions, void* const* grad_state_in,
+                         int semantics, void* workspace, int64_t workspace_bytes, const excenv_launch_opts_t* opts,
+                         void* stream) {
+  return sim_ahead_vjp_call("excenv_sim_ahead_vjp", false, env, solver, dtype, B, K, substeps, props, control, obs_stepsize, env_tau,
+                            actions, action_layout, state_traj, grad_obs_traj, grad_state_traj, grad_last_state, grad_actions,
+                            grad_state_in, semantics, workspace, workspace_bytes, opts, stream, nullptr);
+}
+
+int excenv_sim_ahead_vjp_params(int env, int solver, int dtype, int64_t B, int64_t K, int32_t substeps,
+                                const excenv_props_t* props, const excenv_control_t* control, double obs_stepsize,
+                                double env_tau, const void* actions, int action_layout, const void* const* state_traj,
+                                const void* grad_obs_traj, const void* const* grad_state_traj,
+                                const void* const* grad_last_state, void* grad_actions, void* const* grad_state_in,
+                                int semantics, void* workspace, int64_t workspace_bytes, const excenv_launch_opts_t* opts,
+                                void* stream, void* const* grad_params) {
+  return sim_ahead_vjp_call("excenv_sim_ahead_vjp_params", true, env, solver, dtype, B, K, substeps, props, control, obs_stepsize,
+                            env_tau, actions, action_layout, state_traj, grad_obs_traj, grad_state_traj, grad_last_state,
+                            grad_actions, grad_state_in, semantics, workspace, workspace_bytes, opts, stream, grad_params);
+}
+
+int excenv_param_differentiable(int env, int index) {
+  const EnvVTable* t = table_public(env);
+  if (!t || index < 0 || index >= t->P) return -1;
+  return vjp_param_differentiable(env, index) ? 1 : 0;
+}
+
+int64_t excenv_param_grad_sum_workspace_bytes(int dtype, int64_t B, int32_t n) {
+  if ((dtype != EXCENV_F32 && dtype != EXCENV_F64) || B < 0 || n < 0 || n > EXCENV_MAX_STATIC) return -1;
+  return param_sum_workspace_bytes(B, n);
+}
+
+int excenv_param_grad_sum(int dtype, int64_t B, int32_t n, const void* const* per_env_ptrs, void* out, void* workspace,
+                          int64_t workspace_bytes, void* stream) {
+  const char* fn = "excenv_param_grad_sum";
+  if ((dtype != EXCENV_F32 && dtype != EXCENV_F64) || B < 0 || n < 0 || n > EXCENV_MAX_STATIC) { set_error("%s: bad argument", fn); return EXCENV_EINVAL; }
+  if (n == 0) return EXCENV_OK;
+  if (!per_env_ptrs || !out || !workspace) { set_error("%s: NULL argument", fn); return EXCENV_ENULL; }
+  for (int j = 0; j < n; ++j)
+    if (!per_env_ptrs[j] && B > 0) { set_error("%s: per_env_ptrs[%d] is NULL", fn, j); return EXCENV_ENULL; }
+  const int64_t need = param_sum_workspace_bytes(B, n);
+  if (workspace_bytes < need || align_of(workspace) < 8) {
+    set_error("%s: needs an 8-byte aligned workspace of %lld bytes (excenv_param_grad_sum_workspace_bytes)", fn, (long long)need);
+    return EXCENV_EINVAL;
+  }
+  int rc = launch_param_sum(dtype, B, n, per_env_ptrs, out, workspace, (hipStream_t)stream);
+  if (rc) set_error("%s: launch failed", fn);
+  return rc;
 }
 
 int excenv_rew_trunc_term(int env, int dtype, int64_t B, int64_t rows, const excenv_props_t* props,

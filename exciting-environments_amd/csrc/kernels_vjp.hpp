@@ -21,6 +21,11 @@ template <typename T, class M> struct VjpArgs {
   T* g_state_in[M::S];      // [B]
   T dt, env_tau, adv_coef, lin_stop;
 };
+// The PGRAD instantiations' arguments: one [B] output per static-parameter leaf, nullptr where a leaf is not wanted
+template <typename T, class M> struct VjpParamArgs : VjpArgs<T, M> {
+  T* g_params[M::P];
+};
+template <typename T, class M, bool PGRAD> using VjpKernelArgs = std::conditional_t<PGRAD, VjpParamArgs<T, M>, VjpArgs<T, M>>;
 
 // fp64: the reverse pass evaluates sin / cos with devmath.hpp's lean routine (registers and code size; the Jacobians move by
 // rounding only), fp32 with the forward's own
@@ -68,12 +73,21 @@ template <class M, typename T, int SOLVER, int V> constexpr bool vjp_late_cotang
   return (SOLVER != EXCENV_EULER && vjp_rebuild_stages<M, T>()) || (M::IS_PMSM && V > 1);
 }
 
+// PGRAD: where the parameter accumulators live. The fp64 RK instantiations of the four-leaf models and PMSM (the ones that already
+// rebuild their stages to stay within 256 registers; PMSM Tsit5 has one register to spare) have no room for P more fp64 values
+// across the step: their accumulators sit in LDS, which the reverse kernel does not use otherwise — one private run of P | 1 elements
+// per lane (an odd stride: the 32 lanes of a ds_read_b64 group hit distinct banks), added to in place by every transposed stage.
+// Everywhere else they are registers. (Both this and the scheduling barriers of models.hpp are needed: either alone spills.)
+template <class M, typename T, int SOLVER> constexpr bool vjp_pgrad_in_lds() { return SOLVER != EXCENV_EULER && vjp_rebuild_stages<M, T>(); }
+
 // Adjoint of rk_step (rk.hpp) over Tableau<SOLVER>: recomputes the stage states from the step's starting point y0, then walks
 // the stages in reverse. lam: in = cotangent of the step's result, out = cotangent of y0. ub / u1b: cotangents of the held action
 // and of the action the c_i == 1 stages read (the caller routes u1b to the row that stage read). wb += cotangent of omega_el.
-template <class M, int SOLVER, typename T>
+// PGRAD: every stage's transposed f also adds its parameter columns to pb[M::P].
+template <class M, int SOLVER, bool PGRAD = false, typename T>
 __device__ __forceinline__ void rk_step_vjp(const T (&y0)[M::NY], const T (&u)[M::A], const T (&u1)[M::A], const Ctx<T, M>& c,
-                                            const T (&st)[M::S], T (&lam)[M::NY], T (&ub)[M::A], T (&u1b)[M::A], T& wb) {
+                                            const T (&st)[M::S], T (&lam)[M::NY], T (&ub)[M::A], T (&u1b)[M::A], T& wb,
+                                            T* pb = nullptr) {
   constexpr int NY = M::NY, A = M::A;
   constexpr bool LEAN = vjp_lean_trig<T>();
 #pragma unroll
@@ -82,7 +96,8 @@ __device__ __forceinline__ void rk_step_vjp(const T (&y0)[M::NY], const T (&u)[M
   if constexpr (SOLVER == EXCENV_EULER) {
 #pragma unroll
     for (int j = 0; j < NY; ++j) fb[j] = lam[j] * c.dt;
-    M::template f_vjp<LEAN>(y0, u, c, st, fb, yb, tb, wb);
+    if constexpr (PGRAD) M::template f_vjp<LEAN, true>(y0, u, c, st, fb, yb, tb, wb, pb);
+    else M::template f_vjp<LEAN>(y0, u, c, st, fb, yb, tb, wb);
 #pragma unroll
     for (int j = 0; j < NY; ++j) lam[j] = lam[j] + yb[j];
 #pragma unroll
@@ -130,8 +145,13 @@ __device__ __forceinline__ void rk_step_vjp(const T (&y0)[M::NY], const T (&u)[M
       if (REBUILD) { EXCENV_STAGE_STATE(s, y, y0r) }
 #pragma unroll
       for (int j = 0; j < NY; ++j) fb[j] = kb[s][j] * c.dt;
-      if (TB::c_is_one(s)) M::template f_vjp<LEAN>(y, u1, c, st, fb, yb, tb, wb);
-      else M::template f_vjp<LEAN>(y, u, c, st, fb, yb, tb, wb);
+      if constexpr (PGRAD) {
+        if (TB::c_is_one(s)) M::template f_vjp<LEAN, true>(y, u1, c, st, fb, yb, tb, wb, pb);
+        else M::template f_vjp<LEAN, true>(y, u, c, st, fb, yb, tb, wb, pb);
+      } else {
+        if (TB::c_is_one(s)) M::template f_vjp<LEAN>(y, u1, c, st, fb, yb, tb, wb);
+        else M::template f_vjp<LEAN>(y, u, c, st, fb, yb, tb, wb);
+      }
 #pragma unroll
       for (int j = 0; j < NY; ++j) {
         if (vjp_y_passive<M>(j)) continue;
@@ -156,13 +176,15 @@ __device__ __forceinline__ void rk_step_vjp(const T (&y0)[M::NY], const T (&u)[M
 // row s1. sb: in = cotangent of the carried state after the step, out = before it. a / a1: the action rows k / k1 of the step;
 // gk / gk1: their gradients' contributions (overwritten). PMSM under AHEAD carries more than the state: sb[0..1] is the cotangent of
 // prev_clip (it moves back one row per step), sb[6] collects omega_el's, geps0 the initial angle's (every clip reads
-// eps0 + t_k * omega_el).
-template <class M, int SOLVER, bool AHEAD, typename T>
+// eps0 + t_k * omega_el). PGRAD: pb[M::P] += the step's parameter columns (post where the carried state is post-processed, every
+// stage of the solver, every clip).
+template <class M, int SOLVER, bool AHEAD, bool PGRAD = false, typename T>
 __device__ __forceinline__ void env_step_vjp(const T (&s0)[M::S], const T (&s1)[M::S], const T (&a)[M::A], const T (&a1)[M::A],
                                              int64_t k, int64_t k1, const Ctx<T, M>& c, T eps0, T (&sb)[M::S], T& geps0,
-                                             T (&gk)[M::A], T (&gk1)[M::A]) {
+                                             T (&gk)[M::A], T (&gk1)[M::A], T* pb = nullptr) {
   constexpr int NY = M::NY, A = M::A;
   constexpr bool LEAN = vjp_lean_trig<T>();
+  if constexpr (PGRAD && !AHEAD) M::post_pvjp(s1, c, sb, pb);
   if constexpr (!AHEAD) M::post_vjp(s1, c, sb);  // the carried state is the post-processed one
   T y0[NY], lam[NY], u[A], u1[A], ub[A], u1b[A];
   T wb = T(0);
@@ -171,7 +193,7 @@ __device__ __forceinline__ void env_step_vjp(const T (&s0)[M::S], const T (&s1)[
   if constexpr (!M::IS_PMSM) {
     u[0] = denormalize(a[0], c.amin[0], c.amax[0]);
     u1[0] = AHEAD ? denormalize(a1[0], c.amin[0], c.amax[0]) : u[0];
-    rk_step_vjp<M, SOLVER>(y0, u, u1, c, s0, lam, ub, u1b, wb);
+    rk_step_vjp<M, SOLVER, PGRAD>(y0, u, u1, c, s0, lam, ub, u1b, wb, pb);
     M::set_y(sb, lam);
     const T ds = T(0.5) * (c.amax[0] - c.amin[0]);  // d denormalize / d a
     gk[0] = ub[0] * ds;
@@ -197,7 +219,7 @@ __device__ __forceinline__ void env_step_vjp(const T (&s0)[M::S], const T (&s1)[
       u1[1] = u[1];
       if constexpr (NEXT_CLIP) M::template constraint<LEAN>(a1, ang1, om, c, u1);
     }
-    rk_step_vjp<M, SOLVER>(y0, u, u1, c, s0, lam, ub, u1b, wb);
+    rk_step_vjp<M, SOLVER, PGRAD>(y0, u, u1, c, s0, lam, ub, u1b, wb, pb);
     M::set_y(sb, lam);
     sb[6] = sb[6] + wb;
     T ucb[2], ucb1[2] = {T(0), T(0)};
@@ -221,7 +243,7 @@ __device__ __forceinline__ void env_step_vjp(const T (&s0)[M::S], const T (&s1)[
     // the transposed clip re-evaluates the clip at opaque copies of its inputs: identified with the evaluation above, its rotation,
     // sector and clamp intermediates would stay in registers across the whole RK adjoint
     const T ao[2] = {vjp_opaque(a[0]), vjp_opaque(a[1])};
-    M::template constraint_vjp<LEAN>(ao, vjp_opaque(ang), om, c, ucb, gk, eb, wc);
+    M::template constraint_vjp<LEAN, PGRAD>(ao, vjp_opaque(ang), om, c, ucb, gk, eb, wc, pb);
     if constexpr (AHEAD) {
       geps0 = geps0 + eb;
       sb[6] = sb[6] + (eb * t_k + wc);
@@ -233,7 +255,7 @@ __device__ __forceinline__ void env_step_vjp(const T (&s0)[M::S], const T (&s1)[
       if (!dead) {
         T eb1 = T(0), wc1 = T(0);
         const T a1o[2] = {vjp_opaque(a1[0]), vjp_opaque(a1[1])};
-        M::template constraint_vjp<LEAN>(a1o, vjp_opaque(ang1), om, c, ucb1, gk1, eb1, wc1);
+        M::template constraint_vjp<LEAN, PGRAD>(a1o, vjp_opaque(ang1), om, c, ucb1, gk1, eb1, wc1, pb);
         geps0 = geps0 + eb1;
         sb[6] = sb[6] + (eb1 * t_k1 + wc1);
       }
@@ -246,8 +268,10 @@ __device__ __forceinline__ void env_step_vjp(const T (&s0)[M::S], const T (&s1)[
 // per action row (the `substeps` contributions of a row are summed in registers). The loads of the next iteration are requested
 // before the step's arithmetic, index clamped so that they are unconditional (DESIGN.md §4.1 "Pipeline"). Registers are
 // component-major ([component][environment]): a 16-byte load lands in place.
-template <class M, typename T, int SOLVER, bool AHEAD, int V>
-__global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(2))) sim_ahead_vjp_kernel(const VjpArgs<T, M> ka) {
+// PGRAD: the static-parameter gradients pbv[P][V] stay in registers for the whole trajectory (like PMSM's omega_el cotangent) and
+// leave after row 0, one coalesced [B] store per requested leaf; the batch sum is a launch of its own (param_sum.hip).
+template <class M, typename T, int SOLVER, bool AHEAD, int V, bool PGRAD = false>
+__global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(2))) sim_ahead_vjp_kernel(const VjpKernelArgs<T, M, PGRAD> ka) {
   constexpr int S = M::S, A = M::A, O = M::O;
   constexpr bool LEAN = vjp_lean_trig<T>();
   static_assert(!M::HAS_LUT, "no reverse mode for the saturated PMSM");
@@ -302,6 +326,23 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(2)))
 #pragma unroll
   for (int v = 0; v < V; ++v) om_c[v] = T(0);
   if constexpr (M::IS_PMSM) load_v<T, V>((ka.straj[6] + blk0) + lane, om_c);
+  // PGRAD: gradient w.r.t. the static parameters, per environment: registers, or (vjp_pgrad_in_lds) the lane's own run of LDS
+  constexpr bool PLDS = PGRAD && vjp_pgrad_in_lds<M, T, SOLVER>();
+  constexpr int NPB = (PGRAD && !PLDS) ? M::P : 1;
+  T pbv[NPB][V];
+#pragma unroll
+  for (int j = 0; j < NPB; ++j)
+#pragma unroll
+    for (int v = 0; v < V; ++v) pbv[j][v] = T(0);
+  T* pbl = nullptr;
+  if constexpr (PLDS) {
+    static_assert(V == 1, "the LDS accumulators belong to one environment per lane");
+    constexpr int PSTRIDE = M::P | 1;
+    __shared__ T pbs[BLOCK * PSTRIDE];
+    pbl = &pbs[threadIdx.x * PSTRIDE];
+#pragma unroll
+    for (int j = 0; j < M::P; ++j) pbl[j] = T(0);
+  }
 
   // cotangent of a saved row -> cotangent of the carried state: r = observe^T gob + gst, through post^T where rows are post-processed
   auto add_row = [&](const T (&svh)[S][V], T (&r)[S], int v) __attribute__((always_inline)) {
@@ -309,6 +350,16 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(2)))
       T s1[S];
 #pragma unroll
       for (int j = 0; j < S; ++j) s1[j] = svh[j][v];
+      if constexpr (PLDS) {
+        M::post_pvjp(s1, c, r, pbl);
+      } else if constexpr (PGRAD && M::IS_PMSM) {  // the torque of the saved row reads l_d, l_q, psi_p
+        T pl[M::P];
+#pragma unroll
+        for (int j = 0; j < M::P; ++j) pl[j] = pbv[j][v];
+        M::post_pvjp(s1, c, r, pl);
+#pragma unroll
+        for (int j = 0; j < M::P; ++j) pbv[j][v] = pl[j];
+      }
       M::post_vjp(s1, c, r);
       if constexpr (M::IS_PMSM) {  // the saved buffer columns: prev_clip with dead time, zeros without
         r[0] = dead ? r[0] : T(0);
@@ -447,7 +498,18 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(2)))
         a0[q] = ac[q][v];
         a1[q] = ah[q][v];
       }
-      env_step_vjp<M, SOLVER, AHEAD>(s0, s1, a0, a1, k, k1, c, eps0[v], sbv, geps0[v], g0, g1);
+      if constexpr (PLDS) {
+        env_step_vjp<M, SOLVER, AHEAD, true>(s0, s1, a0, a1, k, k1, c, eps0[v], sbv, geps0[v], g0, g1, pbl);
+      } else if constexpr (PGRAD) {
+        T pl[M::P];
+#pragma unroll
+        for (int j = 0; j < M::P; ++j) pl[j] = pbv[j][v];
+        env_step_vjp<M, SOLVER, AHEAD, true>(s0, s1, a0, a1, k, k1, c, eps0[v], sbv, geps0[v], g0, g1, pl);
+#pragma unroll
+        for (int j = 0; j < M::P; ++j) pbv[j][v] = pl[j];
+      } else {
+        env_step_vjp<M, SOLVER, AHEAD>(s0, s1, a0, a1, k, k1, c, eps0[v], sbv, geps0[v], g0, g1);
+      }
 #pragma unroll
       for (int j = 0; j < S; ++j) sb[j][v] = sbv[j];
 #pragma unroll
@@ -509,6 +571,18 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(2)))
   }
 #pragma unroll
   for (int j = 0; j < S; ++j) store_v<T, V>((ka.g_state_in[j] + blk0) + lane, sb[j]);
+  if constexpr (PGRAD) {
+#pragma unroll
+    for (int j = 0; j < M::P; ++j) {
+      if (ka.g_params[j] == nullptr) continue;
+      if constexpr (PLDS) {
+        const T one[1] = {pbl[j]};
+        store_v<T, 1>((ka.g_params[j] + blk0) + lane, one);
+      } else {
+        store_v<T, V>((ka.g_params[j] + blk0) + lane, pbv[j]);
+      }
+    }
+  }
 }
 
 // The raw levels of the tank under EXCENV_SEM_AHEAD (vjp.hpp vjp_needs_raw_rows): the forward's own steps (env_advance_raw) again,
@@ -544,7 +618,7 @@ __global__ void __launch_bounds__(BLOCK) vjp_raw_rows_kernel(const VjpArgs<T, M>
 
 // Packs VjpArgs and launches the instantiation the call names (vjp.hpp vjp_instantiated): every other combination is an error
 template <class M, typename T> static int launch_vjp(const VjpCall& vc) {
-  VjpArgs<T, M> ka;
+  VjpParamArgs<T, M> ka;  // the plain launch passes its VjpArgs part
   std::memset(&ka, 0, sizeof(ka));
   if (fill_props<T, M>(ka.kp, vc.props)) {
     set_error("excenv_sim_ahead_vjp: per-environment property arrays are not supported");
@@ -575,6 +649,8 @@ template <class M, typename T> static int launch_vjp(const VjpCall& vc) {
   ka.env_tau = (T)vc.env_tau;
   ka.adv_coef = (T)coef;
   ka.lin_stop = (T)(vc.env_tau * (double)(vc.K > 0 ? vc.K - 1 : 0));
+  const bool pgrad = vc.grad_params != nullptr;
+  for (int j = 0; pgrad && j < M::P; ++j) ka.g_params[j] = (T*)vc.grad_params[j];
   if (vc.B == 0) return EXCENV_OK;
   const dim3 grid((unsigned)((vc.B / vc.V + BLOCK - 1) / BLOCK)), block(BLOCK);
   const hipStream_t stream = (hipStream_t)vc.stream;
@@ -587,17 +663,20 @@ template <class M, typename T> static int launch_vjp(const VjpCall& vc) {
       ka.straj[0] = (const T*)vc.raw_rows;
     }
   }
-  const bool launched = vjp_instantiated(vc.semantics, M::ID, (int)sizeof(T), vc.solver, M::HAS_LUT, vc.V) && with_solver(vc.solver, [&](auto solver) {
+  const bool launched = vjp_instantiated(vc.semantics, M::ID, (int)sizeof(T), vc.solver, M::HAS_LUT, vc.V, pgrad) && with_solver(vc.solver, [&](auto solver) {
     return with_flag(ahead, [&](auto ah) {
       return with_const<1, 2, 4>(vc.V, [&](auto v) {
-        constexpr int SOLVER = decltype(solver)::value, VV = decltype(v)::value;
-        constexpr bool AH = decltype(ah)::value;
-        if constexpr (!vjp_instantiated(AH ? EXCENV_SEM_AHEAD : EXCENV_SEM_STEP, M::ID, (int)sizeof(T), SOLVER, M::HAS_LUT, VV)) {
-          return false;
-        } else {
-          hipLaunchKernelGGL((sim_ahead_vjp_kernel<M, T, SOLVER, AH, VV>), grid, block, 0, stream, ka);
-          return true;
-        }
+        return with_flag(pgrad, [&](auto pg) {
+          constexpr int SOLVER = decltype(solver)::value, VV = decltype(v)::value;
+          constexpr bool AH = decltype(ah)::value, PG = decltype(pg)::value;
+          if constexpr (!vjp_instantiated(AH ? EXCENV_SEM_AHEAD : EXCENV_SEM_STEP, M::ID, (int)sizeof(T), SOLVER, M::HAS_LUT, VV, PG)) {
+            return false;
+          } else {
+            const VjpKernelArgs<T, M, PG>& kk = ka;
+            hipLaunchKernelGGL((sim_ahead_vjp_kernel<M, T, SOLVER, AH, VV, PG>), grid, block, 0, stream, kk);
+            return true;
+          }
+        });
       });
     });
   });
@@ -605,7 +684,7 @@ template <class M, typename T> static int launch_vjp(const VjpCall& vc) {
     set_error("excenv_sim_ahead_vjp: no kernel instantiation (semantics %d, %d-byte elements, V=%d)", vc.semantics, (int)sizeof(T), vc.V);
     return EXCENV_EINVAL;
   }
-  g_last_launch = vjp_name(vc.V);
+  g_last_launch = vjp_name(vc.V, pgrad);
   return check_launch("excenv_sim_ahead_vjp");
 }
 

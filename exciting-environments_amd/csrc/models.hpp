@@ -64,6 +64,13 @@ template <typename T, class M> __device__ __forceinline__ void prep_ctx(Ctx<T, M
 //   observe_vjp(sv, c, gob, r): r += (d observe / d st)^T gob
 // Subgradient conventions: a clamp / clip has derivative 0 on its boundary, sign_of has derivative 0, the tank's
 // sqrt term has derivative 0 where h <= 0. The InvDiv denominators of the forward are reused.
+// Parameter columns (PG = true, the PGRAD kernels): the same sweeps also transpose with respect to the static parameters,
+//   f_vjp<LEAN, true>(..., pb): pb[j] += (df / d P[j])^T fb, through the InvDiv denominators that are functions of the parameters too
+//   post_pvjp(sv, c, r, pb): pb += (d post / d P)^T r (PMSM's torque; called in front of post_vjp, which consumes r)
+//   constraint_vjp<LEAN, true>(..., pb): pb += (d uc / d P)^T ucb (PMSM's u_dc, visible where the hexagon clip is active)
+// Integer leaves (PMSM's p and deadtime) and leaves f never reads (acrobot's l_2) are never written: they stay exactly 0.
+// Every parameter block sits between two scheduling barriers: left free, the scheduler interleaves it with the stage's state adjoint
+// and the fp64 RK instantiations spill (cart-pole Tsit5: 344 bytes of scratch without them, 219 registers with them).
 // Transpose of normalize_field: d ob / d x = 2 / (smax - smin)
 template <typename T, class M> __device__ __forceinline__ T normalize_field_vjp(const Ctx<T, M>& c, int j, T g) {
   return c.nrm[j].div(T(2) * g, c.fastdiv);
@@ -90,15 +97,26 @@ template <typename T> struct Pendulum {
     dy[1] = c.den[0].div(u[0] + l * m * g * sin_x<LEAN>(y[0]), c.fastdiv);  // / (m * (l * l))
     dy[0] = y[1];
   }
-  template <bool LEAN = false> __device__ static __forceinline__ void f_vjp(const T (&y)[NY], const T (&)[A], const C& c, const T (&)[S], const T (&fb)[NY],
-                                               T (&yb)[NY], T (&ub)[A], T&) {
+  template <bool LEAN = false, bool PG = false> __device__ static __forceinline__ void f_vjp(const T (&y)[NY], const T (&u)[A], const C& c, const T (&)[S], const T (&fb)[NY],
+                                               T (&yb)[NY], T (&ub)[A], T&, T* pb = nullptr) {
     const T g = c.P[0], l = c.P[1], m = c.P[2];
     const T q = c.den[0].div(fb[1], c.fastdiv);  // fb[1] / (m * (l * l))
     yb[0] = q * (l * m * g * cos_x<LEAN>(y[0]));
     yb[1] = fb[0];
     ub[0] = q;
+    if constexpr (PG) {  // dy[1] = N / D, N = u + l m g sin, D = m l^2
+      __builtin_amdgcn_sched_barrier(0);
+      const T sn = sin_x<LEAN>(y[0]);
+      const T d_b = -(q * c.den[0].div(u[0] + l * m * g * sn, c.fastdiv));
+      const T qs = q * sn;
+      pb[0] = pb[0] + qs * (l * m);
+      pb[1] = pb[1] + (qs * (m * g) + d_b * (T(2) * m * l));
+      pb[2] = pb[2] + (qs * (l * g) + d_b * (l * l));
+      __builtin_amdgcn_sched_barrier(0);
+    }
   }
   __device__ static __forceinline__ void post_vjp(const T (&)[S], const C&, T (&)[S]) {}  // wrap: derivative 1
+  __device__ static __forceinline__ void post_pvjp(const T (&)[S], const C&, const T (&)[S], T*) {}
   template <bool LEAN = false> __device__ static __forceinline__ void observe_vjp(const T (&)[S], const C& c, const T (&gob)[O], T (&r)[S]) {
     observe_fields_vjp<T, Pendulum>(c, gob, r);
   }
@@ -123,15 +141,23 @@ template <typename T> struct MassSpringDamper {
     dy[1] = c.den[0].div(u[0] - d * y[1] - k * y[0], c.fastdiv);  // / m
     dy[0] = y[1];
   }
-  template <bool LEAN = false> __device__ static __forceinline__ void f_vjp(const T (&)[NY], const T (&)[A], const C& c, const T (&)[S], const T (&fb)[NY],
-                                               T (&yb)[NY], T (&ub)[A], T&) {
+  template <bool LEAN = false, bool PG = false> __device__ static __forceinline__ void f_vjp(const T (&y)[NY], const T (&u)[A], const C& c, const T (&)[S], const T (&fb)[NY],
+                                               T (&yb)[NY], T (&ub)[A], T&, T* pb = nullptr) {
     const T d = c.P[0], k = c.P[1];
     const T q = c.den[0].div(fb[1], c.fastdiv);  // fb[1] / m
     yb[0] = -(k * q);
     yb[1] = fb[0] - d * q;
     ub[0] = q;
+    if constexpr (PG) {
+      __builtin_amdgcn_sched_barrier(0);
+      pb[0] = pb[0] - q * y[1];
+      pb[1] = pb[1] - q * y[0];
+      pb[2] = pb[2] - q * c.den[0].div(u[0] - d * y[1] - k * y[0], c.fastdiv);
+      __builtin_amdgcn_sched_barrier(0);
+    }
   }
   __device__ static __forceinline__ void post_vjp(const T (&)[S], const C&, T (&)[S]) {}
+  __device__ static __forceinline__ void post_pvjp(const T (&)[S], const C&, const T (&)[S], T*) {}
   template <bool LEAN = false> __device__ static __forceinline__ void observe_vjp(const T (&)[S], const C& c, const T (&gob)[O], T (&r)[S]) {
     observe_fields_vjp<T, MassSpringDamper>(c, gob, r);
   }
@@ -177,8 +203,8 @@ template <typename T> struct CartPole {
     dy[3] = d_omega;
   }
   // reverse sweep over the expression tree of f, same grouping (sign_of: derivative 0)
-  template <bool LEAN = false> __device__ static __forceinline__ void f_vjp(const T (&y)[NY], const T (&u)[A], const C& c, const T (&)[S], const T (&fb)[NY],
-                                               T (&yb)[NY], T (&ub)[A], T&) {
+  template <bool LEAN = false, bool PG = false> __device__ static __forceinline__ void f_vjp(const T (&y)[NY], const T (&u)[A], const C& c, const T (&)[S], const T (&fb)[NY],
+                                               T (&yb)[NY], T (&ub)[A], T&, T* pb = nullptr) {
     const T mu_p = c.P[0], mu_c = c.P[1], l = c.P[2], m_p = c.P[3], g = c.P[5];
     const T velocity = y[1], theta = y[2], omega = y[3];
     T s, co;
@@ -211,8 +237,29 @@ template <typename T> struct CartPole {
     yb[2] = s_b * co - co_b * s;
     yb[3] = omega_b;
     ub[0] = u_b;
+    if constexpr (PG) {  // the denominators m_c + m_p (mass) and m_p * l (d1) are functions of the parameters
+      __builtin_amdgcn_sched_barrier(0);
+      const T sg = sign_of(velocity);
+      const T x = (omega * omega) * s - d_omega * co;
+      const T d_velocity = by_mass.div(u[0] + m_p * l * x - mu_c * sg, c.fastdiv);
+      const T fr = c.den[1].div(mu_p * omega, c.fastdiv);
+      const T z = by_mass.div(m_p * (co * co), c.fastdiv);
+      const T w2s = (omega * omega) * s;
+      T mass_b = -(t * d_velocity) - n1_b * a_n;
+      const T d1_b = c.den[1].div(num_b * fr, c.fastdiv);
+      const T z_b = -(den_b * l);
+      mass_b = mass_b - by_mass.div(z_b * z, c.fastdiv);
+      pb[0] = pb[0] - c.den[1].div(num_b * omega, c.fastdiv);
+      pb[1] = pb[1] + (n1_b - t) * sg;
+      pb[2] = pb[2] + (t * (m_p * x) - n1_b * (m_p * w2s) + d1_b * m_p + den_b * (T(4.0 / 3.0) - z));
+      pb[3] = pb[3] + (t * (l * x) - n1_b * (l * w2s) + d1_b * l + by_mass.div(z_b * (co * co), c.fastdiv) + mass_b);
+      pb[4] = pb[4] + mass_b;
+      pb[5] = pb[5] + num_b * s;
+      __builtin_amdgcn_sched_barrier(0);
+    }
   }
   __device__ static __forceinline__ void post_vjp(const T (&)[S], const C&, T (&)[S]) {}
+  __device__ static __forceinline__ void post_pvjp(const T (&)[S], const C&, const T (&)[S], T*) {}
   template <bool LEAN = false> __device__ static __forceinline__ void observe_vjp(const T (&)[S], const C& c, const T (&gob)[O], T (&r)[S]) {
     observe_fields_vjp<T, CartPole>(c, gob, r);
   }
@@ -262,8 +309,8 @@ template <typename T> struct Acrobot {
     dy[3] = d_omega_2;
   }
   // reverse sweep over the expression tree of f, same grouping
-  template <bool LEAN = false> __device__ static __forceinline__ void f_vjp(const T (&y)[NY], const T (&u)[A], const C& c, const T (&)[S], const T (&fb)[NY],
-                                               T (&yb)[NY], T (&ub)[A], T&) {
+  template <bool LEAN = false, bool PG = false> __device__ static __forceinline__ void f_vjp(const T (&y)[NY], const T (&u)[A], const C& c, const T (&)[S], const T (&fb)[NY],
+                                               T (&yb)[NY], T (&ub)[A], T&, T* pb = nullptr) {
     const T g = c.P[0], l_1 = c.P[1], m_1 = c.P[3], m_2 = c.P[4], l_c1 = c.P[5], l_c2 = c.P[6], I_1 = c.P[7], I_2 = c.P[8];
     const T theta_1 = y[0], theta_2 = y[1], omega_1 = y[2], omega_2 = y[3];
     T s2, c2;
@@ -315,8 +362,26 @@ template <typename T> struct Acrobot {
     yb[2] = fb[0] + om1_b;
     yb[3] = fb[1] + om2_b;
     ub[0] = w_b;
+    if constexpr (PG) {  // l_2 (P[2]) is not read by f: its gradient stays exactly 0
+      __builtin_amdgcn_sched_barrier(0);
+      const T d22_b = r_b / d_12;
+      const T kap_b = h1_b * (-s2 * (omega_2 * omega_2) - T(2) * s2 * omega_1 * omega_2) + h2_b * (s2 * (omega_1 * omega_1));
+      const T al_b = phi1_b * cA, be_b = (phi1_b + phi2_b) * cB;
+      pb[0] = pb[0] + (al_b * (m_1 * l_c1 + m_2 * l_1) + be_b * (m_2 * l_c2));
+      pb[1] = pb[1] + (d11_b * (m_2 * (T(2) * l_1 + T(2) * l_c2 * c2)) + d12_b * (m_2 * l_c2 * c2) + kap_b * (m_2 * l_c2) + al_b * (g * m_2));
+      pb[3] = pb[3] + (d11_b * (l_c1 * l_c1) + al_b * (g * l_c1));
+      pb[4] = pb[4] + (d11_b * (l_1 * l_1 + l_c2 * l_c2 + T(2) * l_1 * l_c2 * c2) + d12_b * (l_c2 * l_c2 + l_1 * l_c2 * c2) +
+                       d22_b * (l_c2 * l_c2) + kap_b * (l_1 * l_c2) + al_b * (g * l_1) + be_b * (l_c2 * g));
+      pb[5] = pb[5] + (d11_b * (T(2) * m_1 * l_c1) + al_b * (g * m_1));
+      pb[6] = pb[6] + (d11_b * (m_2 * (T(2) * l_c2 + T(2) * l_1 * c2)) + d12_b * (m_2 * (T(2) * l_c2 + l_1 * c2)) +
+                       d22_b * (T(2) * m_2 * l_c2) + kap_b * (m_2 * l_1) + be_b * (m_2 * g));
+      pb[7] = pb[7] + d11_b;
+      pb[8] = pb[8] + (d11_b + d12_b + d22_b);
+      __builtin_amdgcn_sched_barrier(0);
+    }
   }
   __device__ static __forceinline__ void post_vjp(const T (&)[S], const C&, T (&)[S]) {}
+  __device__ static __forceinline__ void post_pvjp(const T (&)[S], const C&, const T (&)[S], T*) {}
   template <bool LEAN = false> __device__ static __forceinline__ void observe_vjp(const T (&)[S], const C& c, const T (&gob)[O], T (&r)[S]) {
     observe_fields_vjp<T, Acrobot>(c, gob, r);
   }
@@ -345,15 +410,25 @@ template <typename T> struct FluidTank {
     dy[0] = c.den[0].div(u[0], c.fastdiv) - c_d * orifice_area / base_area * xsqrt(T(2) * g * h);
   }
   // d sqrt(2 g h) / d h = g / sqrt(2 g h) for h > 0, 0 for h <= 0 (the clamp's boundary included)
-  template <bool LEAN = false> __device__ static __forceinline__ void f_vjp(const T (&y)[NY], const T (&)[A], const C& c, const T (&)[S], const T (&fb)[NY],
-                                               T (&yb)[NY], T (&ub)[A], T&) {
+  template <bool LEAN = false, bool PG = false> __device__ static __forceinline__ void f_vjp(const T (&y)[NY], const T (&u)[A], const C& c, const T (&)[S], const T (&fb)[NY],
+                                               T (&yb)[NY], T (&ub)[A], T&, T* pb = nullptr) {
     const T base_area = c.P[0], orifice_area = c.P[1], c_d = c.P[2], g = c.P[3];
     const bool wet = y[0] > T(0);
     const T root = xsqrt(T(2) * g * (wet ? y[0] : T(1)));
     yb[0] = wet ? -(fb[0] * (c_d * orifice_area / base_area * (g / root))) : T(0);
     ub[0] = c.den[0].div(fb[0], c.fastdiv);
+    if constexpr (PG) {  // the sqrt term contributes 0 where h <= 0; u / base_area always
+      __builtin_amdgcn_sched_barrier(0);
+      const T rb = wet ? fb[0] * root : T(0);  // -(cotangent of the coefficient c_d * orifice_area / base_area)
+      pb[0] = pb[0] + (rb * (c_d * orifice_area / base_area / base_area) - ub[0] * c.den[0].div(u[0], c.fastdiv));
+      pb[1] = pb[1] - rb * (c_d / base_area);
+      pb[2] = pb[2] - rb * (orifice_area / base_area);
+      pb[3] = pb[3] - (wet ? fb[0] * (c_d * orifice_area / base_area * (y[0] / root)) : T(0));
+      __builtin_amdgcn_sched_barrier(0);
+    }
   }
   __device__ static __forceinline__ void post_vjp(const T (&sv)[S], const C&, T (&r)[S]) { r[0] = (sv[0] > T(0)) ? r[0] : T(0); }
+  __device__ static __forceinline__ void post_pvjp(const T (&)[S], const C&, const T (&)[S], T*) {}
   template <bool LEAN = false> __device__ static __forceinline__ void observe_vjp(const T (&)[S], const C& c, const T (&gob)[O], T (&r)[S]) {
     observe_fields_vjp<T, FluidTank>(c, gob, r);
   }
@@ -388,8 +463,8 @@ template <typename T> struct Pmsm {
     dy[2] = omega_el;
   }
   // wb += (df / d omega_el)^T fb: omega_el is a constant of the trajectory that every step reads
-  template <bool LEAN = false> __device__ static __forceinline__ void f_vjp(const T (&y)[NY], const T (&)[A], const C& c, const T (&st)[S], const T (&fb)[NY],
-                                               T (&yb)[NY], T (&ub)[A], T& wb) {
+  template <bool LEAN = false, bool PG = false> __device__ static __forceinline__ void f_vjp(const T (&y)[NY], const T (&u)[A], const C& c, const T (&st)[S], const T (&fb)[NY],
+                                               T (&yb)[NY], T (&ub)[A], T& wb, T* pb = nullptr) {
     const T r_s = c.P[1], l_d = c.P[2], l_q = c.P[3], psi_p = c.P[4];
     const T omega_el = st[6];
     const InvDiv<T>* d[2] = {&c.den[0], &c.den[1]};  // / l_d, / l_q
@@ -402,6 +477,17 @@ template <typename T> struct Pmsm {
     ub[0] = q[0];
     ub[1] = q[1];
     wb = wb + (l_q * y[1] * q[0] - (l_d * y[0] + psi_p) * q[1] + fb[2]);
+    if constexpr (PG) {  // the slopes themselves: d (n / l) / d l = -(n / l) / l
+      __builtin_amdgcn_sched_barrier(0);
+      const T nn[2] = {u[0] + omega_el * l_q * y[1] - r_s * y[0], u[1] - omega_el * (l_d * y[0] + psi_p) - r_s * y[1]};
+      T dy[2];
+      div_all<2, T>(d, nn, dy, c.fastdiv);
+      pb[1] = pb[1] - (q[0] * y[0] + q[1] * y[1]);
+      pb[2] = pb[2] - (q[0] * dy[0] + q[1] * (omega_el * y[0]));
+      pb[3] = pb[3] + (q[0] * (omega_el * y[1]) - q[1] * dy[1]);
+      pb[4] = pb[4] - q[1] * omega_el;
+      __builtin_amdgcn_sched_barrier(0);
+    }
   }
   // pmsm_env.py:365-375
   __device__ static __forceinline__ T torque(T i_d, T i_q, const C& c) {
@@ -419,6 +505,14 @@ template <typename T> struct Pmsm {
     r[3] = r[3] + r[5] * (T(1.5) * p * (l_d - l_q) * sv[4]);
     r[4] = r[4] + r[5] * (T(1.5) * p * (psi_p + (l_d - l_q) * sv[3]));
     r[5] = T(0);
+  }
+  // parameter columns of post at the saved row (in front of post_vjp: r[5] is the torque's incoming cotangent)
+  __device__ static __forceinline__ void post_pvjp(const T (&sv)[S], const C& c, const T (&r)[S], T* pb) {
+    const T p = c.P[0];
+    const T tq = r[5] * (T(1.5) * p * sv[4]);
+    pb[2] = pb[2] + tq * sv[3];
+    pb[3] = pb[3] - tq * sv[3];
+    pb[4] = pb[4] + tq;
   }
   // transpose of observe: [i_d, i_q, omega_el, torque, cos eps, sin eps, u_d_buffer, u_q_buffer]
   template <bool LEAN = false> __device__ static __forceinline__ void observe_vjp(const T (&sv)[S], const C& c, const T (&gob)[O], T (&r)[S]) {
@@ -506,9 +600,9 @@ template <typename T> struct Pmsm {
   // Transpose of constraint (rotation -> hexagon clip -> rotation back) at (a, eps, omega_el): ab += (d uc / d a)^T ucb,
   // eb += (d uc / d eps)^T ucb, wb += (d uc / d omega_el)^T ucb (through the predicted angle). The sector bits are piecewise
   // constant (derivative 0); a clamp passes its cotangent strictly inside its bounds only.
-  template <bool LEAN = false, class CC>
+  template <bool LEAN = false, bool PG = false, class CC>
   __device__ static __forceinline__ void constraint_vjp(const T (&a)[A], T eps, T omega_el, const CC& c, const T (&ucb)[2],
-                                                        T (&ab)[A], T& eb, T& wb) {
+                                                        T (&ab)[A], T& eb, T& wb, T* pb = nullptr) {
     const T u_dc = c.P[5];
     const T half_dc = u_dc / T(2);
     const T u_d = denormalize(a[0], c.amin[0], c.amax[0]);
@@ -562,6 +656,12 @@ template <typename T> struct Pmsm {
     wb = wb + adv_b * c.adv_coef;
     ab[0] = ab[0] + nd_b * sc * (T(0.5) * (c.amax[0] - c.amin[0]));
     ab[1] = ab[1] + nq_b * sc * (T(0.5) * (c.amax[1] - c.amin[1]));
+    if constexpr (PG) {  // u_dc scales the clip's input down (sc = 2 / u_dc) and its output up: the two cancel where nothing clips
+      __builtin_amdgcn_sched_barrier(0);
+      const T half_b = ucb[0] * (cs * al + sn * be) + ucb[1] * (cs * be - sn * al) - (nd_b * u_d + nq_b * u_q) * sc * sc;
+      pb[5] = pb[5] + T(0.5) * half_b;
+      __builtin_amdgcn_sched_barrier(0);
+    }
   }
 };
 

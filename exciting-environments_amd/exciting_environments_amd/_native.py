@@ -103,6 +103,12 @@ PROTOTYPES = {
     # grad_state_in, semantics, workspace, workspace_bytes, opts, stream
     "excenv_sim_ahead_vjp": (_ci, [_ci, _ci, _ci, _i64, _i64, _i32, _vp, _vp, _cd, _cd, _vp, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _ci,
                                    _vp, _i64, _vp, _vp]),
+    # the same, then grad_params (behind `stream`: the C order)
+    "excenv_sim_ahead_vjp_params": (_ci, [_ci, _ci, _ci, _i64, _i64, _i32, _vp, _vp, _cd, _cd, _vp, _ci, _vp, _vp, _vp, _vp, _vp, _vp,
+                                          _ci, _vp, _i64, _vp, _vp, _vp]),
+    "excenv_param_differentiable": (_ci, [_ci, _ci]),
+    "excenv_param_grad_sum_workspace_bytes": (_i64, [_ci, _i64, _i32]),
+    "excenv_param_grad_sum": (_ci, [_ci, _i64, _i32, _vp, _vp, _vp, _i64, _vp]),
     "excenv_transpose": (_ci, [_ci, _i64, _i64, _vp, _vp, _vp]),
     "excenv_rew_trunc_term": (_ci, [_ci, _ci, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _ci, _vp]),
     "excenv_state_from_observation": (_ci, [_ci, _ci, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
@@ -229,6 +235,16 @@ def _launch(name: str, on: torch.Tensor, what: str, *args):
     fn = getattr(lib(), name)
     with _on_device(on.device):
         rc = fn(*args, _raw_stream(on.device))
+    if rc != 0:
+        _check(rc, name)
+
+
+def _launch_then(name: str, on: torch.Tensor, what: str, args, tail):
+    """_launch for an entry point whose C arguments continue behind `stream`: fn(*args, stream, *tail)."""
+    _require_device(on, what)
+    fn = getattr(lib(), name)
+    with _on_device(on.device):
+        rc = fn(*args, _raw_stream(on.device), *tail)
     if rc != 0:
         _check(rc, name)
 

@@ -41,14 +41,15 @@ class TrajectoryLaunchMixin:
     # Larger outputs keep one allocation per returned array so that dropping the states frees their memory.
     _SHARED_TRAJ_BYTES = 32 << 20
 
-    def _run_sim_ahead(self, init_state, actions, env_properties, obs_stepsize, action_stepsize, B, want_gym=False, out=None):
+    def _run_sim_ahead(self, init_state, actions, env_properties, obs_stepsize, action_stepsize, B, want_gym=False, out=None,
+                       packed=None):
         S, A, OW = self.physical_state_dim, self.action_dim, self._obs_dim()
         actions = torch.as_tensor(actions)
         K = actions.shape[-2]
         sub = self._n_substeps(K, obs_stepsize, action_stepsize)
         N = K * sub
         rows = N + 1
-        props, keep = self._props_for(env_properties, B)
+        props, keep = packed if packed is not None else self._props_for(env_properties, B)  # packed: a differentiable call's own
         st_in = [self._t(getattr(init_state.physical_state, n), (B,)) for n in self.STATE_FIELDS]
         control, refs = self._control(init_state, (B,))
         dt, dev = self.dtype, self.device

@@ -205,6 +205,12 @@ class CoreEnvironment(TrajectoryLaunchMixin, TrajectoryVjpMixin, ABC):
         return p, keep
 
     def _props_for(self, env_properties, B: int):
+        # a scalar tensor leaf (a parameter an optimiser updates in place) is read at every call: the cache below is keyed by the
+        # identity of env_properties and would keep the value of the first call
+        sp = getattr(env_properties, "static_params", None)
+        if sp is not None and any(isinstance(getattr(sp, n, None), torch.Tensor) and getattr(sp, n).numel() == 1
+                                  for n in self.PARAM_FIELDS):
+            return self._pack_props(env_properties, B)
         if env_properties is self.env_properties and B == self.batch_size:
             if self._packed_props is None or self._packed_for is not env_properties:
                 self._packed_props = self._pack_props(env_properties, B)

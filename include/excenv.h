@@ -277,7 +277,7 @@ int excenv_sim_ahead_fuses_actions(int env, int solver, int dtype, int64_t B, in
  * opts->envs_per_lane: 0 = the forward's batch rule, 1 or 16 / sizeof(dtype) = forced (the wide form needs B % that == 0 and
  * 16-byte aligned arrays). Derivatives of clamps / clips are 0 on the boundary, of sign 0, of the tank's sqrt term 0 at h <= 0.
  * Not supported, rejected before any launch: the saturated PMSM (pmsm_lut), EXCENV_SEM_AHEAD_ACCUMULATED_T, the tiled layout and
- * per-environment property arrays (EXCENV_EUNSUPPORTED); gradients w.r.t. properties do not exist.
+ * per-environment property arrays (EXCENV_EUNSUPPORTED). Gradients w.r.t. the static parameters: excenv_sim_ahead_vjp_params below.
  * excenv_last_launch() then reports "sim_ahead_vjp_kernel (V=1|V=2|V=4)".
  * Workspace: excenv_sim_ahead_vjp_workspace_bytes_for (addition) is the size for a given call — the transposed actions and,
  * for the tank under EXCENV_SEM_AHEAD with RK4 / Tsit5, the raw levels [N+1][B] a pass in front of the reverse launch restores
@@ -294,6 +294,36 @@ int excenv_sim_ahead_vjp(int env, int solver, int dtype, int64_t B, int64_t K, i
                          const void* const* grad_last_state, void* grad_actions, void* const* grad_state_in,
                          int semantics, void* workspace, int64_t workspace_bytes, const excenv_launch_opts_t* opts,
                          void* stream);
+
+/* ---- gradients w.r.t. the static parameters (what jax.grad of the reference's vmap_sim_ahead w.r.t.
+ * env_properties.static_params gives; additions, same ABI version: a binder probes for the symbols).
+ * excenv_sim_ahead_vjp_params is excenv_sim_ahead_vjp — same arguments, same rejections, and bit for bit the same grad_actions and
+ * grad_state_in — whose one launch (the PGRAD instantiation of the reverse kernel) also accumulates, per environment, the
+ * gradient w.r.t. every requested leaf of props->static_params:
+ *   grad_params : EXCENV_MAX_STATIC entries, each a 16-byte aligned [B] array of the working dtype (out) or NULL = not wanted.
+ *                 All NULL, a non-NULL entry beyond the model's parameter count or for an integer leaf (PMSM's p and deadtime):
+ *                 EXCENV_EINVAL, naming the entry. The properties themselves stay broadcast values: the [B] outputs are the
+ *                 per-environment terms of the batch gradient (excenv_param_grad_sum adds them up). A leaf the vector field never
+ *                 reads (acrobot's l_2) gets exact zeros. PMSM's u_dc is visible only where the hexagon clip is active; the
+ *                 normalisation bounds are not differentiated.
+ * excenv_last_launch() then reports "sim_ahead_vjp_kernel (V=1|V=2|V=4, PGRAD)"; a forced opts->envs_per_lane without a PGRAD
+ * form is EXCENV_EINVAL as for the plain call.
+ * excenv_param_differentiable: 1 if static parameter `index` of `env` has a gradient, 0 if it is an integer leaf, -1 for a bad
+ * env or index.
+ * excenv_param_grad_sum: out[j] = sum over the batch of per_env_ptrs[j][0..B) for j < n <= EXCENV_MAX_STATIC (host array of device
+ * pointers; out: n device elements of `dtype`). Two small launches, fp64 accumulation, no atomics: the same B gives the same bits
+ * on every run. workspace: excenv_param_grad_sum_workspace_bytes(dtype, B, n) bytes of device memory, 8-byte aligned. */
+int excenv_sim_ahead_vjp_params(int env, int solver, int dtype, int64_t B, int64_t K, int32_t substeps,
+                                const excenv_props_t* props, const excenv_control_t* control, double obs_stepsize,
+                                double env_tau, const void* actions, int action_layout, const void* const* state_traj,
+                                const void* grad_obs_traj, const void* const* grad_state_traj,
+                                const void* const* grad_last_state, void* grad_actions, void* const* grad_state_in,
+                                int semantics, void* workspace, int64_t workspace_bytes, const excenv_launch_opts_t* opts,
+                                void* stream, void* const* grad_params);
+int excenv_param_differentiable(int env, int index);
+int64_t excenv_param_grad_sum_workspace_bytes(int dtype, int64_t B, int32_t n);
+int excenv_param_grad_sum(int dtype, int64_t B, int32_t n, const void* const* per_env_ptrs, void* out, void* workspace,
+                          int64_t workspace_bytes, void* stream);
 
 /* out[n][m] = in[m][n] for a row-major M x N matrix of the given dtype (the conversion kernel used above). */
 int excenv_transpose(int dtype, int64_t M, int64_t N, const void* in, void* out, void* stream);

@@ -1,0 +1,247 @@
+"""Host side of the parameter gradients (no GPU): the C ABI declares and exports the new entry points, rejects what it must before any
+launch, the PGRAD instantiations of sim_ahead_vjp_kernel exist and stay within the register / scratch / loop-size budget, the plain
+instantiations kept the register counts of the commit before (tests/golden/vjp_resources_parent.json), and the form rule."""
+import ctypes
+import importlib.util
+import json
+import os
+import re
+import shutil
+import subprocess
+
+import pytest
+import torch
+
+from exciting_environments_amd import EnvironmentRegistry, _native
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+i64, i32, vp, dbl = ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_double
+EINVAL, ENULL, EUNSUPPORTED = -1, -2, -4
+ENVS = {"pendulum": 0, "mass_spring_damper": 1, "cartpole": 2, "acrobot": 3, "fluid_tank": 4, "pmsm": 5}
+
+
+def _tool():
+    spec = importlib.util.spec_from_file_location("loop_code_size", os.path.join(ROOT, "tools", "loop_code_size.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_header_declares_and_library_exports_the_new_entry_points():
+    hdr = open(os.path.join(ROOT, "include", "excenv.h")).read()
+    assert re.search(r"\bint\s+excenv_sim_ahead_vjp_params\s*\(", hdr)
+    assert re.search(r"\bint\s+excenv_param_differentiable\s*\(", hdr)
+    assert re.search(r"\bint\s+excenv_param_grad_sum\s*\(", hdr)
+    assert re.search(r"\bint64_t\s+excenv_param_grad_sum_workspace_bytes\s*\(", hdr)
+    assert re.search(r"#define\s+EXCENV_ABI_VERSION\s+7\b", hdr)  # additions: a binder probes for the symbols
+    lib = ctypes.CDLL(_native.library_path())
+    for name in ("excenv_sim_ahead_vjp_params", "excenv_param_differentiable", "excenv_param_grad_sum", "excenv_param_grad_sum_workspace_bytes"):
+        assert hasattr(lib, name) and name in _native.PROTOTYPES, name
+    assert len(_native.PROTOTYPES["excenv_sim_ahead_vjp"][1]) == 23
+    assert _native.PROTOTYPES["excenv_sim_ahead_vjp_params"][1][:23] == _native.PROTOTYPES["excenv_sim_ahead_vjp"][1]
+    assert len(_native.PROTOTYPES["excenv_sim_ahead_vjp_params"][1]) == 24
+    assert len(_native.PROTOTYPES["excenv_param_grad_sum"][1]) == 8 and len(_native.PROTOTYPES["excenv_param_grad_sum_workspace_bytes"][1]) == 3
+    assert _native.lib().excenv_abi_version() == 7
+    wb = _native.lib().excenv_param_grad_sum_workspace_bytes
+    assert wb(_native.F32, 1000, 3) > 0 and wb(_native.F32, 1000, 3) % 256 == 0
+    assert wb(_native.F64, (1 << 17) + 1, 9) >= 8 * 9 * 33
+    assert wb(7, 1000, 3) == -1 and wb(_native.F32, -1, 3) == -1 and wb(_native.F32, 10, 10) == -1
+
+
+def test_param_differentiable_per_model():
+    fn = _native.lib().excenv_param_differentiable
+    for reg in EnvironmentRegistry:
+        env = reg.make(batch_size=4, device="cpu")
+        for j, name in enumerate(env.PARAM_FIELDS):
+            want = 0 if (env.ENV_ID == ENVS["pmsm"] and name in ("p", "deadtime")) else 1
+            assert fn(env.ENV_ID, j) == want, (reg, name)
+        assert fn(env.ENV_ID, len(env.PARAM_FIELDS)) == -1 and fn(env.ENV_ID, -1) == -1
+    assert fn(17, 0) == -1
+
+
+def _call(env=0, solver=0, dtype=0, B=4, K=3, sub=1, props=None, semantics=_native.SEM_AHEAD, layout=_native.LAYOUT_LANE_MAJOR,
+          opts=None, ws=None, ws_bytes=0, want=(0,), params_null=False):
+    lib = _native.lib()
+    p = props if props is not None else _native.Props()
+    one = (ctypes.c_void_p * 8)(*([64] * 8))
+    gp = (ctypes.c_void_p * _native.MAX_STATIC)(*[64 if j in want else None for j in range(_native.MAX_STATIC)])
+    rc = lib.excenv_sim_ahead_vjp_params(env, solver, dtype, i64(B), i64(K), i32(sub), ctypes.byref(p), None, dbl(1e-4), dbl(1e-4), vp(64),
+                                         layout, one, vp(64), one, one, vp(64), one, semantics, ws, i64(ws_bytes),
+                                         None if opts is None else ctypes.byref(opts), None, None if params_null else gp)
+    return rc, lib.excenv_last_error()
+
+
+def test_rejections_happen_before_any_launch():
+    """No GPU here: anything that reached a launch would fail differently (EXCENV_EHIP) or crash on the fake pointers."""
+    rc, msg = _call(want=())
+    assert rc == EINVAL and b"grad_params" in msg and b"NULL" in msg
+    rc, msg = _call(params_null=True)
+    assert rc == ENULL
+    rc, msg = _call(env=5, want=(0,))  # PMSM's p
+    assert rc == EINVAL and b"grad_params[0]" in msg and b"integer" in msg
+    rc, msg = _call(env=5, want=(1, 6))  # deadtime
+    assert rc == EINVAL and b"grad_params[6]" in msg and b"integer" in msg
+    rc, msg = _call(env=0, want=(0, 3))  # the pendulum has three parameters
+    assert rc == EINVAL and b"grad_params[3]" in msg
+    # every rejection of the plain call, same codes and words
+    p = _native.Props()
+    lut = _native.PmsmLut(4, 4, 64, 64, 64)
+    p.pmsm_lut = ctypes.pointer(lut)
+    rc, msg = _call(env=5, props=p, want=(1,))
+    assert rc == EUNSUPPORTED and b"saturated" in msg
+    rc, msg = _call(semantics=_native.SEM_AHEAD_ACCUMULATED_T)
+    assert rc == EUNSUPPORTED and b"ACCUMULATED_T" in msg
+    p = _native.Props()
+    p.static_params[1].per_env = 64
+    rc, msg = _call(props=p)
+    assert rc == EUNSUPPORTED and b"per-environment" in msg
+    p = _native.Props()
+    p.state_max[0].per_env = 64
+    rc, msg = _call(props=p)
+    assert rc == EUNSUPPORTED and msg
+    rc, msg = _call(layout=_native.LAYOUT_TILED)
+    assert rc == EUNSUPPORTED and b"tiled" in msg
+    rc, msg = _call(layout=_native.LAYOUT_ENV_MAJOR)
+    assert rc == EINVAL and b"workspace" in msg
+    rc, msg = _call(env=4, solver=1)
+    assert rc == EINVAL and b"excenv_sim_ahead_vjp_workspace_bytes_for" in msg
+    rc, msg = _call(env=4, solver=1, ws=vp(256), ws_bytes=255)
+    assert rc == EINVAL and b"256 bytes" in msg
+    assert _call(env=9)[0] == EINVAL and _call(semantics=7)[0] == EINVAL and _call(K=-1)[0] == EINVAL and _call(sub=0)[0] == EINVAL
+    # a forced width without a PGRAD form is refused by name: PMSM Euler fp32 has its wide form for the plain call only
+    rc, msg = _call(env=5, want=(1,), opts=_native.LaunchOpts(4, 0, 0, 0))
+    assert rc == EINVAL and b"envs_per_lane = 4 is not available" in msg
+    rc, msg = _call(env=3, solver=2, opts=_native.LaunchOpts(4, 0, 0, 0))
+    assert rc == EINVAL and b"envs_per_lane" in msg
+    # the batch sum
+    lib = _native.lib()
+    ptrs = (ctypes.c_void_p * 3)(64, 64, 64)
+    assert lib.excenv_param_grad_sum(7, i64(4), i32(3), ptrs, vp(64), vp(256), i64(256), None) == EINVAL
+    assert lib.excenv_param_grad_sum(0, i64(4), i32(10), ptrs, vp(64), vp(256), i64(256), None) == EINVAL
+    assert lib.excenv_param_grad_sum(0, i64(4), i32(3), None, vp(64), vp(256), i64(256), None) == ENULL
+    assert lib.excenv_param_grad_sum(0, i64(4), i32(3), ptrs, vp(64), vp(256), i64(8), None) == EINVAL
+    assert b"excenv_param_grad_sum_workspace_bytes" in lib.excenv_last_error()
+
+
+PLAIN = re.compile(r"^(_ZN6excenv20sim_ahead_vjp_kernelI.*Li[124])ELb0E(EEv.*)$")
+PGRAD = re.compile(r"^(_ZN6excenv20sim_ahead_vjp_kernelI.*Li([124]))ELb1E(EEv.*)$")
+MODELS = {"8PendulumI": "pendulum", "16MassSpringDamperI": "mass_spring_damper", "8CartPoleI": "cartpole", "7AcrobotI": "acrobot",
+          "9FluidTankI": "fluid_tank", "4PmsmI": "pmsm"}
+
+
+def _args(sym):
+    """model, element size, solver name, V of an instantiation's symbol"""
+    m = re.match(r"_ZN6excenv20sim_ahead_vjp_kernelINS_(\d+[A-Za-z]+I)([fd])EE[fd]Li([012])ELb[01]ELi([124])E", sym)
+    assert m, sym
+    return MODELS[m.group(1)], 4 if m.group(2) == "f" else 8, ("euler", "rk4", "tsit5")[int(m.group(3))], int(m.group(4))
+
+
+def test_pgrad_instantiations_exist_within_the_budget_and_the_plain_ones_kept_their_registers():
+    from helpers_vjp_params import vjp_pgrad_wide_ok
+
+    mod = _tool()
+    if not (os.path.exists(mod.OBJDUMP) and os.path.exists(mod.READELF)):
+        pytest.skip("llvm-objdump / llvm-readelf not available")
+    res = {k: v for k, v in mod.kernel_resources().items() if "sim_ahead_vjp_kernel" in k}
+    pgrad = {k: v for k, v in res.items() if PGRAD.match(k)}
+    plain = {k: v for k, v in res.items() if PLAIN.match(k)}
+    assert len(pgrad) + len(plain) == len(res)
+    # six models x three solvers x two semantics x two dtypes at one environment per lane
+    narrow = [k for k in pgrad if _args(k)[3] == 1]
+    assert len(pgrad) >= 72 and len(narrow) == 72, (len(pgrad), len(narrow))
+    # the wide forms exist exactly where vjp_pgrad_wide_ok says so (both semantics each)
+    wide = sorted(_args(k) for k in pgrad if _args(k)[3] > 1)
+    want = sorted((e, elem, s, 16 // elem) for e in MODELS.values() for elem in (4, 8) for s in ("euler", "rk4", "tsit5")
+                  if vjp_pgrad_wide_ok(e, elem, s) for _ in range(2))
+    assert wide == want
+    for e in ("pendulum", "mass_spring_damper", "fluid_tank"):  # the three small models keep their wide form for all solvers
+        assert all(vjp_pgrad_wide_ok(e, elem, s) for elem in (4, 8) for s in ("euler", "rk4", "tsit5"))
+    over = {k: v for k, v in pgrad.items() if v["scratch"] != 0 or v["vgpr"] > 256}
+    for k, v in sorted(over.items()):
+        print(v, k)
+    assert not over, f"{len(over)} of {len(pgrad)} PGRAD instantiations over budget"
+    spans = {k: v for k, v in mod.loop_spans().items() if PGRAD.match(k)}
+    assert len(spans) == len(pgrad)
+    worst = max(spans.items(), key=lambda kv: kv[1][0])
+    print("largest PGRAD loop:", worst, "most registers:", max(v["vgpr"] for v in pgrad.values()))
+    assert worst[1][0] < 60 * 1024
+    # PGRAD == false: the instantiations of the commit before, register for register (their symbols gained the flag only)
+    gold = json.load(open(os.path.join(ROOT, "tests", "golden", "vjp_resources_parent.json")))
+    gold.pop("_comment")
+    now = {}
+    for k, v in plain.items():
+        m = PLAIN.match(k)
+        now[m.group(1)] = [v["vgpr"], v["sgpr"], v["scratch"]]
+    before = {re.match(r"^(.*Li[124])EEEv", k).group(1): v for k, v in gold.items()}
+    assert len(before) == len(gold) == 116
+    assert now == before, {k: (before.get(k), now.get(k)) for k in set(before) | set(now) if before.get(k) != now.get(k)}
+
+
+def test_pgrad_form_rule(tmp_path):
+    """vjp.hpp is host-only: the host compiler builds its constexpr functions alone (static_asserts are the test)"""
+    cxx = shutil.which("g++") or shutil.which("c++")
+    if cxx is None:
+        pytest.skip("no host C++ compiler")
+    src = tmp_path / "t.cpp"
+    src.write_text('''#include "vjp.hpp"
+using namespace excenv;
+static_assert(vjp_pgrad_wide_ok(EXCENV_PENDULUM, 8, EXCENV_TSIT5) && vjp_pgrad_wide_ok(EXCENV_MASS_SPRING_DAMPER, 4, EXCENV_RK4) &&
+              vjp_pgrad_wide_ok(EXCENV_FLUID_TANK, 8, EXCENV_TSIT5), "the three small models keep their wide form for all solvers");
+static_assert(vjp_pgrad_wide_ok(EXCENV_CART_POLE, 8, EXCENV_EULER) && vjp_pgrad_wide_ok(EXCENV_ACROBOT, 4, EXCENV_EULER), "");
+static_assert(!vjp_pgrad_wide_ok(EXCENV_ACROBOT, 8, EXCENV_EULER) && !vjp_pgrad_wide_ok(EXCENV_CART_POLE, 4, EXCENV_RK4), "no plain wide form either");
+static_assert(vjp_wide_ok(EXCENV_PMSM, 4, EXCENV_EULER) && !vjp_pgrad_wide_ok(EXCENV_PMSM, 4, EXCENV_EULER), "PMSM Euler fp32: plain only");
+static_assert(vjp_envs_per_lane(EXCENV_PMSM, EXCENV_EULER, 1 << 20, 4, 0, true, true) == 1, "the call runs one environment per lane");
+static_assert(vjp_envs_per_lane(EXCENV_PMSM, EXCENV_EULER, 1 << 20, 4, 0, true) == 4, "the plain call keeps its form");
+static_assert(vjp_envs_per_lane(EXCENV_PMSM, EXCENV_EULER, 256, 4, 4, true, true) == 0, "forced: refused");
+static_assert(vjp_envs_per_lane(EXCENV_PENDULUM, EXCENV_TSIT5, 1 << 20, 8, 0, true, true) == 2, "the forward's batch rule");
+static_assert(vjp_envs_per_lane(EXCENV_PENDULUM, EXCENV_TSIT5, 1 << 10, 8, 0, true, true) == 1, "");
+static_assert(vjp_envs_per_lane(EXCENV_PENDULUM, EXCENV_TSIT5, 256, 4, 4, true, true) == 4, "forced");
+static_assert(vjp_instantiated(EXCENV_SEM_STEP, EXCENV_PMSM, 8, EXCENV_TSIT5, false, 1, true), "V = 1 everywhere");
+static_assert(!vjp_instantiated(EXCENV_SEM_AHEAD, EXCENV_PMSM, 4, EXCENV_EULER, false, 4, true), "");
+static_assert(vjp_instantiated(EXCENV_SEM_AHEAD, EXCENV_PMSM, 4, EXCENV_EULER, false, 4), "");
+static_assert(!vjp_instantiated(EXCENV_SEM_AHEAD, EXCENV_PMSM, 4, EXCENV_EULER, true, 1, true), "saturated PMSM");
+static_assert(!vjp_param_differentiable(EXCENV_PMSM, 0) && !vjp_param_differentiable(EXCENV_PMSM, 6) && vjp_param_differentiable(EXCENV_PMSM, 5), "");
+static_assert(vjp_param_differentiable(EXCENV_ACROBOT, 2), "l_2 is returned (exact zeros)");
+static_assert(param_sum_groups(1) == 1 && param_sum_groups(4096) == 1 && param_sum_groups(4097) == 2 && param_sum_groups((int64_t)1 << 40) == PSUM_GROUPS, "");
+static_assert(param_sum_workspace_bytes(1000, 3) == 256 && param_sum_workspace_bytes((int64_t)1 << 22, 9) == 18432, "");
+int main() { return 0; }
+''')
+    subprocess.run([cxx, "-std=c++17", "-I", os.path.join(ROOT, "exciting-environments_amd", "csrc"), "-fsyntax-only", str(src)], check=True)
+
+
+def test_param_grads_none_returns_the_two_tuple_and_bad_values_are_refused():
+    import inspect
+
+    env = EnvironmentRegistry.PENDULUM.make(batch_size=4, device="cpu")
+    sig = inspect.signature(env.vmap_sim_ahead_vjp)
+    assert sig.parameters["param_grads"].default is None
+    assert env.last_vjp_launch == ""  # set by every reverse launch, on the thread that enqueued it (autograd's, for backward)
+    actions = torch.zeros(4, 3, 1)
+    with pytest.raises(ValueError, match="param_grads"):
+        env.vmap_sim_ahead_vjp(None, actions, 1e-4, 1e-4, param_grads="mean")
+    # the rejections of the plain call come first, by the same words
+    env.traj_layout = "tiled"
+    with pytest.raises(ValueError, match="tiled"):
+        env.vmap_sim_ahead_vjp(None, actions, 1e-4, 1e-4, param_grads="sum")
+    env = EnvironmentRegistry.PENDULUM.make(batch_size=4, device="cpu", static_params={"g": torch.full((4,), 9.81), "l": 1.0, "m": 1.0})
+    with pytest.raises(ValueError, match="per-environment"):
+        env.vmap_sim_ahead_vjp(None, actions, 1e-4, 1e-4, param_grads="per_env")
+
+
+def test_scalar_tensor_parameters_are_packed_afresh_and_others_keep_the_cache():
+    env = EnvironmentRegistry.PENDULUM.make(batch_size=4, device="cpu")
+    a, _ = env._props_for(env.env_properties, 4)
+    b, _ = env._props_for(env.env_properties, 4)
+    assert a is b  # no tensor leaf: the cache
+    m = torch.tensor(1.5, requires_grad=True)
+    env = EnvironmentRegistry.PENDULUM.make(batch_size=4, device="cpu", static_params={"g": 9.81, "l": 1.0, "m": m})
+    assert [j for j, _ in env._param_leaves()] == [2]
+    a, _ = env._props_for(env.env_properties, 4)
+    assert a.static_params[2].value == 1.5
+    with torch.no_grad():
+        m.mul_(2.0)
+    b, _ = env._props_for(env.env_properties, 4)
+    assert b is not a and b.static_params[2].value == 3.0 and a.static_params[2].value == 1.5
+    env.differentiable = True
+    _, state = env.vmap_reset()
+    assert env._wants_grad(state, torch.zeros(4, 3, 1))
