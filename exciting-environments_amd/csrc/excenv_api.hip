@@ -66,7 +66,7 @@ static int check_opts(const char* fn, const excenv_launch_opts_t*& o) {
   if (!(v == 0 || v == 1 || v == 2 || v == 4)) { set_error("%s: opts.envs_per_lane must be 0, 1, 2 or 4 (got %d)", fn, v); return EXCENV_EINVAL; }
   if (o->env_major_mode < 0 || o->env_major_mode > 3) { set_error("%s: opts.env_major_mode must be 0, 1, 2 or 3", fn); return EXCENV_EINVAL; }
   if (o->lds_pad_bytes < 0 || o->lds_pad_bytes > 150 * 1024) { set_error("%s: opts.lds_pad_bytes out of range", fn); return EXCENV_EINVAL; }
-  if ((o->flags & ~EXCENV_OPT_NO_FUSED_ACTIONS) != 0) { set_error("%s: opts.flags has unknown bits set (0x%x)", fn, (unsigned)o->flags); return EXCENV_EINVAL; }
+  if ((o->flags & ~(EXCENV_OPT_NO_FUSED_ACTIONS | EXCENV_OPT_KEEP_CONSTANT_COLUMNS)) != 0) { set_error("%s: opts.flags has unknown bits set (0x%x)", fn, (unsigned)o->flags); return EXCENV_EINVAL; }
   return EXCENV_OK;
 }
 
@@ -251,6 +251,8 @@ int excenv_sim_ahead_ws(int env, int solver, int dtype, int64_t B, int64_t K, in
   const SimPlan plan = sim_plan(f);
   SimCall sc{solver, dtype, B, K, substeps, props, control, obs_stepsize, env_tau, state_in, actions, action_layout,
              obs_traj, state_traj, traj_layout, last_state, semantics, opts->lds_pad_bytes, gym, (hipStream_t)stream, plan};
+  // the caller's promise about its own lane-major output buffers (a trajectory workspace holds no earlier launch's rows)
+  sc.keep_const = (opts->flags & EXCENV_OPT_KEEP_CONSTANT_COLUMNS) != 0 && traj_layout == EXCENV_LAYOUT_LANE_MAJOR;
   if (!plan.via_workspace) return t->sim(sc);
   // env-major buffers + workspace: transpose in, run the coalesced lane-major kernel, transpose out
   const int64_t w = f.elem, N = K * substeps, OW = t->O + nc;

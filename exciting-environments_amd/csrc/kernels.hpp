@@ -51,6 +51,7 @@ template <typename T, class M> struct SimArgs {
   int32_t substeps;
   int32_t n_control;
   int32_t row_sync;  // one-environment-per-lane instantiations: 1 = a workgroup barrier before the stores of every row, 2 = rows leave through LDS as 16-byte stores (launch.hpp)
+  int32_t keep_const;  // EXCENV_OPT_KEEP_CONSTANT_COLUMNS holds for obs / straj (lane-major, env stride 1; launch.hpp). In what was padding.
   const T* state_in[M::S];
   T* last_state[M::S];
   const T* actions;
@@ -168,6 +169,11 @@ template <typename T, int V> __device__ __forceinline__ void load_v(const T* p, 
 #pragma unroll
     for (int j = 0; j < V; ++j) out[j] = e[j];
   }
+}
+// a and b as bit patterns: a NaN equals itself, -0 differs from +0
+template <typename T> __device__ __forceinline__ bool same_bits(T a, T b) {
+  if constexpr (sizeof(T) == 4) return __builtin_bit_cast(uint32_t, a) == __builtin_bit_cast(uint32_t, b);
+  else return __builtin_bit_cast(uint64_t, a) == __builtin_bit_cast(uint64_t, b);
 }
 template <typename T, int V> __device__ __forceinline__ void store_v(T* p, const T (&in)[V]) {
   if constexpr (V == 1) {
@@ -494,14 +500,18 @@ template <class M, typename T, int V> constexpr size_t aem_lds_bytes() { return 
 // The Euler kernels of cart-pole and acrobot with gym outputs (192 registers with the packed flags): neither HBM nor the vector
 // units are saturated at two waves per SIMD (0.60 … 0.62 of the roof); capped at 168 registers a third wave is resident, at the
 // price of 48 … 128 spilled bytes: cart-pole 4.72 -> 4.56 ms, acrobot 4.81 -> 4.68 (B = 2^22, K = 100, two runs each).
-template <class M, typename T, bool GENERAL, bool AEM, bool LGYM, int STATES, int SOLVER = -1> constexpr int sim_min_waves() {
+template <class M, typename T, bool GENERAL, bool AEM, bool LGYM, int STATES, int SOLVER = -1, bool PLAIN_AHEAD = false, int V = 0> constexpr int sim_min_waves() {
   if (LGYM && (M::ID == EXCENV_ACROBOT || M::ID == EXCENV_CART_POLE) && sizeof(T) == 4 && SOLVER == EXCENV_EULER) return 3;
   if (LGYM && M::ID == EXCENV_ACROBOT && sizeof(T) == 4) return 2;
   if (GENERAL && M::ID == EXCENV_PENDULUM && sizeof(T) == 8) return 2;
   if (AEM && M::IS_PMSM && !M::HAS_LUT && sizeof(T) == 8 && STATES == 0) return 2;
+  // PMSM Euler fp64, observations only, two environments per lane, reference structure (not the accumulated-time kernel): the one
+  // instantiation that the vote of EXCENV_OPT_KEEP_CONSTANT_COLUMNS (sim_ahead_body.inc) took past 256 registers (255 -> 264) — the
+  // second wave per SIMD stays
+  if (V == 2 && PLAIN_AHEAD && !GENERAL && !AEM && !LGYM && M::IS_PMSM && !M::HAS_LUT && sizeof(T) == 8 && STATES == 0 && SOLVER == EXCENV_EULER) return 2;
   return 1;
 }
-#define EXCENV_SIM_KERNEL_ATTR __attribute__((amdgpu_waves_per_eu(sim_min_waves<M, T, GENERAL, AEM, LGYM, STATES, SOLVER>())))
+#define EXCENV_SIM_KERNEL_ATTR __attribute__((amdgpu_waves_per_eu(sim_min_waves<M, T, GENERAL, AEM, LGYM, STATES, SOLVER, AHEAD, V>())))
 // ACC_T (EXCENV_SEM_AHEAD_ACCUMULATED_T): the AHEAD structure on the accumulated-time clock of sim_clock.hpp — per solver step the
 // clock gives the action row of the c_i == 1 stages and the step size, both wave-uniform. Not with the row-major action windows
 // (they assume one row per step) or the lean gym outputs: sim_plan.hpp never picks those forms for it. Its own kernel name

@@ -55,6 +55,7 @@ struct SimCall {
   const excenv_traj_gym_t* gym;  // optional reward / terminated / truncated trajectories
   hipStream_t stream;
   SimPlan plan;  // sim_plan(): the form of the trajectory kernel
+  bool keep_const = false;  // EXCENV_OPT_KEEP_CONSTANT_COLUMNS on the caller's own lane-major trajectory buffers
 };
 
 struct TrajGymCall {
@@ -472,6 +473,8 @@ template <class M, typename T> static int launch_sim(const SimCall& sc) {
   if (emr) ka.a_wg = p.period;
   if (!env_major) {
     ka.row_sync = p.row_sync;
+    // time-constant columns may stay as an earlier launch left them (sim_ahead_body.inc): lane-major rows, adjacent environments
+    ka.keep_const = (sc.keep_const && sc.traj_layout == EXCENV_LAYOUT_LANE_MAJOR && ka.o_sb == 1 && ka.s_sb == 1) ? 1 : 0;
     // element offset of workgroup w's first env in each stream
     const int64_t wg_envs = (int64_t)p.threads * p.V;
     auto wg_off = [&](int layout, int64_t sb, int64_t per_tile) -> int64_t {

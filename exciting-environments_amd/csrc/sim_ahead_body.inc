@@ -177,6 +177,52 @@
   const unsigned s_lane = (V == 1) ? threadIdx.x * (unsigned)ka.s_sb : lane_env;
   const bool with_states = (STATES < 0) ? (ka.straj[0] != nullptr) : (STATES != 0);
 
+  // EXCENV_OPT_KEEP_CONSTANT_COLUMNS (include/excenv.h). omega_el is a constant of a PMSM trajectory (Pmsm::f only reads st[6]), so
+  // every row of its state leaf and of observation column 2 (its normalised value) repeats row 0. The caller says that the buffers
+  // still hold an earlier launch's rows: where row 0 of both columns is, bit for bit, what this launch would store there, all their
+  // rows are, and the wave leaves the two columns alone — 8 of the 68 bytes per environment-step of a write-bound kernel. Decided once
+  // per wave (one scalar: two scalar branches per row, no per-lane predicate); a wave in which any environment differs — one that was
+  // reset or given another speed — writes everything, as a launch without the flag does. Not in the row-major-action form (AEM): its
+  // counted wait needs every store of a row behind a window fill (NSTORE below). Not with the lean gym outputs or the accumulated-time
+  // clock either: there the vote cost registers (fp64 gym outputs 254 -> 290) for launches that are not write-bound to begin with.
+  constexpr bool KEEPC = M::IS_PMSM && !M::HAS_LUT && !GENERAL && !AEM && !LGYM && !ACC_T;
+  constexpr int KC_OBS = 2, KC_LEAF = 6;  // Pmsm::observe: ob[2] = normalize(st[6])
+  bool keep = false;
+  if constexpr (KEEPC) {
+    if (__builtin_expect(ka.keep_const != 0, 1)) {  // (launch.hpp: lane-major rows, environment stride 1); kept in line: steady state
+      T kept_o[V], kept_s[V];
+      load_v<T, V>(o_blk + KC_OBS * ka.o_sc + o_lane, kept_o);
+      if (with_states) load_v<T, V>(ka.straj[KC_LEAF] + s_blk + s_lane, kept_s);
+      bool same = true;
+#pragma unroll
+      for (int v = 0; v < V; ++v) {
+        // what save_row(0) stores into the two columns, through the calls it makes: the same values, the same bits (the dead-time rows
+        // it puts into sv[0 .. 1] reach neither omega_el nor its observation column)
+        T sv0[S], ob0[O];
+#pragma unroll
+        for (int j = 0; j < S; ++j) sv0[j] = st[v][j];
+        if constexpr (AHEAD) M::post(sv0, c);
+        M::observe(sv0, c, ob0);
+        same = same & same_bits(kept_o[v], ob0[KC_OBS]);  // (& : no branch per environment)
+        if (with_states) same = same & same_bits(kept_s[v], sv0[KC_LEAF]);
+      }
+      keep = __builtin_amdgcn_readfirstlane((int)(__builtin_amdgcn_ballot_w64(!same) == 0)) != 0;
+      if constexpr (V == 1 && !ROW_BARRIER) {
+        // rows that leave through LDS are stored by the workgroup's waves for each other: the vote is the workgroup's (whole
+        // workgroups only take that path, sim_plan.hpp: every thread is here). The word used is free until row 0 is staged.
+        if (ka.row_sync == 2) {
+          unsigned* vote = reinterpret_cast<unsigned*>(excenv_smem);
+          if (threadIdx.x == 0) *vote = 0u;
+          __syncthreads();
+          if (!keep && (threadIdx.x & 63u) == 0u) *vote = 1u;
+          __syncthreads();
+          keep = __builtin_amdgcn_readfirstlane(*vote) == 0u;
+          __syncthreads();
+        }
+      }
+    }
+  }
+
   // ---- save row n: observation, (control columns), state leaves, (gym outputs); returns the saved state in sv ----
   auto save_row = [&](int64_t n, T (&sv)[V][S]) {
 #pragma unroll
@@ -240,6 +286,9 @@
         for (int u = wv; u < NS * CH; u += NW) {
           const int q = u / CH;
           const unsigned e = (unsigned)(u % CH) * (64u * VE) + ln * VE;
+          if constexpr (KEEPC) {
+            if (keep && (q == KC_OBS || q == OWr + KC_LEAF)) continue;  // (no state leaves: q < OWr)
+          }
           T tmp[VE];
           load_v<T, VE>(buf + q * NT + e, tmp);
           T* dst = (q < OWr) ? orow + q * ka.o_sc : ka.straj[q - OWr] + s_blk + n * ka.s_sk;
@@ -255,6 +304,9 @@
     if (direct) {
 #pragma unroll
       for (int q = 0; q < O; ++q) {
+        if constexpr (KEEPC) {
+          if (keep && q == KC_OBS) continue;
+        }
         T tmp[V];
 #pragma unroll
         for (int v = 0; v < V; ++v) tmp[v] = ob[v][q];
@@ -274,6 +326,9 @@
       if (with_states) {
 #pragma unroll
         for (int j = 0; j < S; ++j) {
+          if constexpr (KEEPC) {
+            if (keep && j == KC_LEAF) continue;
+          }
           T tmp[V];
 #pragma unroll
           for (int v = 0; v < V; ++v) tmp[v] = sv[v][j];

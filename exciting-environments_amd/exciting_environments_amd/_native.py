@@ -26,6 +26,7 @@ SEM_AHEAD_ACCUMULATED_T = 2  # opt-in: diffrax's accumulated-time clock as the C
 SEMANTICS = {"step": SEM_STEP, "ahead": SEM_AHEAD, "ahead_accumulated_t": SEM_AHEAD_ACCUMULATED_T}
 F32, F64 = 0, 1
 OPT_NO_FUSED_ACTIONS = 1  # EXCENV_OPT_NO_FUSED_ACTIONS
+OPT_KEEP_CONSTANT_COLUMNS = 2  # EXCENV_OPT_KEEP_CONSTANT_COLUMNS
 ABI_VERSION = 7
 
 _LIB_PATH = os.environ.get(  # EXCENV_HIP_LIB: A/B-test another build of the same library (tuning experiments)

@@ -5,7 +5,7 @@ trajectory buffers lie in physical device memory moves the trajectory kernel by 
 
 Interface used by `CoreEnvironment`:
     StepSlotPool(env):          take(gym, stream, capturing) -> (slots, i)
-    TrajectoryPlacement(env):   acquire(shape ...) -> TrajSet     timed_launch(set, fn, nbytes)     note_launch(set)
+    TrajectoryPlacement(env):   acquire(shape ...) -> TrajSet     launch_into(set, launch, ...)     note_launch(set)
                                 settled     release()     wait_stream(stream) / drain_waits()     memory_budget(...)
 Both hand a buffer out again ONLY when nothing outside can observe it: no Python reference to any of its tensors (sys.getrefcount
 back at the value recorded when the buffer was made), no C++ holder (Tensor._use_count() == 1: autograd, DLPack, a view keeps its
@@ -177,13 +177,44 @@ class StepSlotPool:
 #     `steady_ms` from its second timed launch on.
 class TrajSet:
     __slots__ = ("key", "obs_buf", "st_buf", "lbuf", "observations", "st_views", "last", "obs_ptr", "traj_ptrs", "last_ptrs",
-                 "tens", "storages", "rc0", "use0", "stream", "placement", "ev", "ev_pending", "steady_ms", "first_ms", "uses")
+                 "tens", "storages", "rc0", "use0", "stream", "placement", "ev", "ev_pending", "steady_ms", "first_ms", "uses",
+                 "const_stamp")
 
     def __init__(self, key=None):
         self.key = key
         self.ev, self.ev_pending, self.steady_ms, self.first_ms, self.uses = None, False, None, None, 0
         self.placement = None
         self.rc0 = self.use0 = self.stream = None
+        self.const_stamp = None
+
+    # Constant columns (EXCENV_OPT_KEEP_CONSTANT_COLUMNS, include/excenv.h). A lane-major trajectory launch leaves every row of a
+    # time-constant column (PMSM: omega_el and its observation column) equal to row 0. The stamp says that such a launch of the owning
+    # environment was the last thing enqueued on the set's stream that wrote the set, and holds the version counters of its two
+    # buffers right after it: every in-place torch operation through any view of them moves a counter (views share their base's), so
+    # an unchanged pair means the rows are still that launch's — the next launch may then be told so and skip those columns. What
+    # torch cannot see is not covered: a write through a raw pointer taken from a returned array (a DLPack consumer, a foreign
+    # kernel given data_ptr(), `.data`, which has a counter of its own) — the same class of caveat as a missing record_stream below.
+    # The library's own `out=` launches are such writers too (they go through the caller's arrays, which may be views of a pooled
+    # set, by raw pointer and not through launch_into): so what the stamp knows is "nothing torch can see has written the set since",
+    # not literally "that launch was the last writer". It holds up because every lane-major trajectory launch leaves the constant
+    # columns uniform along the rows and the kernel compares row 0 itself; a writer without that property must clear the stamp.
+    # Buffers allocated under torch.inference_mode() have no version counter (reading it raises): their history cannot be known, so
+    # such a set is never stamped and its launches never carry the flag.
+    def _versions(self):
+        """The two counters, or None where one cannot be read (inference tensors)."""
+        bufs = (self.obs_buf,) if self.st_buf is None else (self.obs_buf, self.st_buf)
+        try:
+            if any(getattr(b, "is_inference", bool)() for b in bufs):
+                return None
+            return tuple(b._version for b in bufs)
+        except RuntimeError:
+            return None
+
+    def stamp_constant_columns(self):
+        self.const_stamp = self._versions()
+
+    def constant_columns_intact(self) -> bool:
+        return self.const_stamp is not None and self.const_stamp == self._versions()
 
     def record_ms(self, ms: float):
         """Time of one real launch into this set. The first one is kept apart (cold clocks / first touch): never a judgement."""
@@ -298,6 +329,19 @@ class TrajectoryPlacement:
         launch_fn()
         ts.ev[1].record()
         ts.ev_pending = True
+
+    def launch_into(self, ts: TrajSet, launch, nbytes: int, lane_major: bool, allow_keep: bool, capturing: bool) -> bool:
+        """The call's own launch into its output set: `launch(obs_ptr, traj_ptrs, last_ptrs, keep)`. keep — the launch may leave the
+        constant columns alone — only for a set whose stamp is intact (TrajSet), never while a graph is being captured (the launch
+        runs when the graph is replayed, whatever has been written by then). Probe launches into candidate blocks (acquire) do not
+        come through here and never carry it; neither does the first launch into a new or replacement set (no stamp yet).
+        Returns whether the launch carried it."""
+        keep = bool(allow_keep and lane_major and not capturing and ts.constant_columns_intact())
+        ts.const_stamp = None  # a launch that raises leaves no promise behind
+        self.timed_launch(ts, lambda: launch(ts.obs_ptr, ts.traj_ptrs, ts.last_ptrs, keep), nbytes)
+        if allow_keep and lane_major and not capturing:  # (switched off: no stamp is kept at all)
+            ts.stamp_constant_columns()
+        return keep
 
     @staticmethod
     def _set_bytes(key) -> int:

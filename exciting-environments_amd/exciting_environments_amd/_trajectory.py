@@ -93,12 +93,16 @@ class TrajectoryLaunchMixin:
         sem = self._semantics_id
         st_in_ptrs = _native._ptrs(st_in)
 
-        def launch(o_ptr, t_ptrs, l_ptrs):  # the trajectory launch of this call into the given output buffers
+        def launch(o_ptr, t_ptrs, l_ptrs, keep=False):  # the trajectory launch of this call into the given output buffers
+            # keep: the buffers still hold an earlier launch's constant columns (only _placement.launch_into says so)
+            o = opts if not keep else _native.launch_opts(
+                opts.envs_per_lane if opts else 0, opts.env_major_mode if opts else 0, opts.lds_pad_bytes if opts else 0,
+                (opts.flags if opts else 0) | _native.OPT_KEEP_CONSTANT_COLUMNS)
             with _native._on_device(dev):
                 _native.sim_ahead_raw(self.ENV_ID, self._solver.id, 0 if dt is torch.float32 else 1, B, K, sub, ctypes.byref(props),
                                       _native._ref(control), float(obs_stepsize), float(self.tau), st_in_ptrs,
                                       actions.data_ptr() if K > 0 else None, a_layout, o_ptr, t_ptrs if want_states else None,
-                                      t_layout, l_ptrs, sem, ws_ptr, ws_bytes if ws_ptr is not None else 0, _native._ref(opts),
+                                      t_layout, l_ptrs, sem, ws_ptr, ws_bytes if ws_ptr is not None else 0, _native._ref(o),
                                       _native._raw_stream(dev), gym_ref)
 
         if provider == "out":
@@ -118,12 +122,14 @@ class TrajectoryLaunchMixin:
             res = self._outputs_plain(t_layout, B, rows, OW, S, want_states)
         observations, st_views, last, obs_ptr, traj_ptrs, last_ptrs, ts = res
 
+        self.last_constant_columns_kept = False
         if ts is None:
             launch(obs_ptr, traj_ptrs, last_ptrs)
         else:
             self._placement.drain_waits()
-            self._placement.timed_launch(ts, lambda: launch(obs_ptr, traj_ptrs, last_ptrs),
-                                         (OW + (S if want_states else 0)) * rows * B * isz)
+            self.last_constant_columns_kept = self._placement.launch_into(
+                ts, launch, (OW + (S if want_states else 0)) * rows * B * isz, t_layout == _LM, self.keep_constant_columns,
+                _native.cuda_is_capturing())
         if want_gym:
             return observations, st_views, last, N, gym_out
         return observations, st_views, last, N

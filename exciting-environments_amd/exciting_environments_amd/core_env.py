@@ -129,6 +129,13 @@ class CoreEnvironment(TrajectoryLaunchMixin, TrajectoryVjpMixin, ABC):
         self.trajectory_pool = True          # False: every large call allocates its outputs (the behaviour up to round 2)
         self.trajectory_placement = "auto"   # "auto": ordered pair, search as fall-back; "search": the search only; "off": none
         self._placement = TrajectoryPlacement(self)
+        # True: a large vmap_sim_ahead call that writes a pooled output set again tells the kernel that the set's time-constant
+        # columns (PMSM: omega_el and its observation column) still hold the previous launch's rows, which then stay untouched where
+        # they already are what the call would store (EXCENV_OPT_KEEP_CONSTANT_COLUMNS; same results, fewer bytes written). Known
+        # through torch's version counters (_placement.TrajSet): a write into a returned array that bypasses torch — through a raw
+        # pointer handed to a DLPack consumer or a foreign kernel — is not seen; set this to False where that happens.
+        self.keep_constant_columns = True
+        self.last_constant_columns_kept = False  # whether the last vmap_sim_ahead launch carried that flag
         self._traj_bcast_cache = None
         self._ws_bytes_cache = None
         self._fused_actions_cache = None

@@ -39,7 +39,8 @@ extern "C" {
  *    excenv_sim_ahead_fuses_actions, excenv_last_launch, excenv_allgather
  * 7: the lane-major truncated-flag trajectory is [row][B][flag] (an environment's flags adjacent; was [row][flag][B]):
  *    excenv_traj_gym_t.truncated of excenv_sim_ahead and the `truncated` output of excenv_rew_trunc_term. Every signature
- *    is unchanged; the env-major layout [B][row][flag] — the reference's — is untouched */
+ *    is unchanged; the env-major layout [B][row][flag] — the reference's — is untouched
+ *    (still 7: EXCENV_OPT_KEEP_CONSTANT_COLUMNS, a flag bit older callers never set) */
 #define EXCENV_ABI_VERSION 7
 
 /* Environment ids. Field orders follow the reference dataclasses. */
@@ -151,8 +152,20 @@ typedef struct {
  *   lds_pad_bytes  : extra dynamic LDS per sim_ahead workgroup (caps resident workgroups per CU; occupancy experiments)
  *   flags          : bit set of EXCENV_OPT_* (0 = defaults; unknown bits are an error)
  *     EXCENV_OPT_NO_FUSED_ACTIONS : row-major actions with lane-major trajectories are transposed through the workspace
- *                                   (or read with generic strides) instead of being read by the trajectory kernel itself */
+ *                                   (or read with generic strides) instead of being read by the trajectory kernel itself
+ *     EXCENV_OPT_KEEP_CONSTANT_COLUMNS : excenv_sim_ahead[_ws] only. The caller guarantees that in the lane-major output buffers
+ *                                   of this call every row of a time-constant column equals that column's row 0, for every
+ *                                   environment — true of buffers an earlier excenv_sim_ahead call of the same shape and layout
+ *                                   has written and nothing has modified since. PMSM (no look-up tables): omega_el is a constant
+ *                                   of a trajectory, so a wave whose environments all find row 0 of the omega_el state leaf and
+ *                                   of observation column 2 bit-equal to what it is about to store there leaves both columns
+ *                                   alone (8 of the 68 bytes per environment-step in fp32); a wave in which any environment
+ *                                   differs writes everything. Results are the same bits either way. Takes no part in choosing
+ *                                   the kernel form; ignored by every other model and by every form but the lean lane-major one
+ *                                   (per-environment properties, control columns written by the kernel, row-major actions read
+ *                                   by the kernel, env-major and tiled trajectories, trajectories that go through a workspace) */
 #define EXCENV_OPT_NO_FUSED_ACTIONS 1
+#define EXCENV_OPT_KEEP_CONSTANT_COLUMNS 2
 typedef struct {
   int32_t envs_per_lane;
   int32_t env_major_mode;

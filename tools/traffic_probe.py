@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """Workload for the rocprofv3 --pmc passes: a calibration copy of known size (to check how FETCH_SIZE /
 WRITE_SIZE count 16-byte-per-lane streams on gfx950, MI355X_MICROARCH.md §HBM) followed by a few launches of
-the headline sim_ahead chunk. Usage: python3 tools/traffic_probe.py [workload] [launches]"""
+the headline sim_ahead chunk. Usage: python3 tools/traffic_probe.py [workload] [launches]
+Prints, per launch, whether it carried EXCENV_OPT_KEEP_CONSTANT_COLUMNS: the first launch into each of the two pooled output
+sets writes everything, the launches after them leave the time-constant columns alone (PMSM) — the dispatches of one pass differ
+in WRITE_SIZE by exactly those columns, in this order. --no-keep: every launch writes everything."""
 import os
 import sys
 
@@ -22,6 +25,7 @@ ap.add_argument("--batch", type=int, default=0)
 ap.add_argument("--chunk", type=int, default=0)
 ap.add_argument("--vec", type=int, default=0)
 ap.add_argument("--path", default="sim_ahead")
+ap.add_argument("--no-keep", action="store_true")
 a = ap.parse_args()
 a.semantics = "ahead"
 torch.cuda.set_device(0)
@@ -37,9 +41,13 @@ env, state, actions, B, Kc, reg, solver, dtype = bench.build_env(a, dev, 0)
 if a.vec:
     from exciting_environments_amd import _native
     env.launch_opts = _native.launch_opts(envs_per_lane=a.vec)
+env.keep_constant_columns = not a.no_keep
+kept = []
 for _ in range(a.launches):
     if a.path == "step":
         obs, state = env.vmap_step(state, actions[:, 0, :].contiguous())
     else:
         obs, states, state = env.vmap_sim_ahead(state, actions, env.tau, env.tau)
+        kept.append(int(env.last_constant_columns_kept))
 torch.cuda.synchronize()
+print("constant columns kept, per launch:", kept, flush=True)
