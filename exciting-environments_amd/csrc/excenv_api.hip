@@ -468,6 +468,75 @@ int excenv_rew_trunc_term(int env, int dtype, int64_t B, int64_t rows, const exc
   return t->traj_gym(gc);
 }
 
+int excenv_rew_reads(int env, int32_t n_control, const int32_t* control_idx, uint8_t reads[EXCENV_MAX_STATE]) {
+  const EnvVTable* t = table_public(env);
+  if (!t) { set_error("excenv_rew_reads: bad env id %d", env); return EXCENV_EINVAL; }
+  if (n_control < 0 || n_control > EXCENV_MAX_CONTROL) { set_error("excenv_rew_reads: bad n_control %d", n_control); return EXCENV_EINVAL; }
+  if (!reads || (n_control > 0 && !control_idx)) { set_error("excenv_rew_reads: NULL argument"); return EXCENV_ENULL; }
+  for (int j = 0; j < n_control; ++j)
+    if (control_idx[j] < 0 || control_idx[j] >= t->S) { set_error("excenv_rew_reads: control_idx[%d] out of range", j); return EXCENV_EINVAL; }
+  uint8_t r[EXCENV_MAX_STATE];
+  reward_reads(env, n_control, control_idx, r);
+  std::copy(r, r + EXCENV_MAX_STATE, reads);
+  return EXCENV_OK;
+}
+
+int excenv_rew_vjp(int env, int dtype, int64_t B, int64_t rows, const excenv_props_t* props,
+                   const excenv_control_t* control, const int64_t* ref_strides, const void* const* state_traj,
+                   int64_t state_env_stride, int64_t state_row_stride, const void* grad_reward, int64_t grad_env_stride,
+                   int64_t grad_row_stride, void* const* grad_state_traj, const excenv_launch_opts_t* opts, void* stream) {
+  const char* fn = "excenv_rew_vjp";
+  if (int rc = check_common(fn, env, 0, dtype, B)) return rc;
+  if (rows < 1) { set_error("%s: rows must be >= 1 (row 0 is the initial state)", fn); return EXCENV_EINVAL; }
+  if (!props || !state_traj || !grad_state_traj || (rows > 1 && !grad_reward)) { set_error("%s: NULL argument", fn); return EXCENV_ENULL; }
+  if (int rc = check_control(fn, env, control)) return rc;
+  if (int rc = check_opts(fn, opts)) return rc;
+  int trc;
+  if (!table_for(env, props, &trc)) return trc;  // a malformed pmsm_lut is rejected as everywhere; a valid one is not read
+  if (B == 0) return EXCENV_OK;  // nothing to write: no launch, whatever the (empty) arrays' addresses are
+  const EnvVTable* t = table_public(env);
+  const int nc = control ? control->n_control : 0;
+  uint8_t reads[EXCENV_MAX_STATE];
+  reward_reads(env, nc, control ? control->control_idx : nullptr, reads);
+  const int elem = dtype == EXCENV_F64 ? 8 : 4;
+  // the fast form: whole lanes, everything lane-major and 16-byte aligned, broadcast properties
+  bool fast_ok = (B % (16 / elem)) == 0 && state_env_stride == 1 && state_row_stride == B &&
+                 (rows == 1 || (grad_env_stride == 1 && grad_row_stride == B && align_of(grad_reward) >= 16));
+  bool any = false;
+  for (int j = 0; j < t->S; ++j) {
+    if (!reads[j]) continue;
+    any = true;
+    if (!state_traj[j]) { set_error("%s: state_traj pointer %d is NULL (the reward reads this leaf)", fn, j); return EXCENV_ENULL; }
+    if (!grad_state_traj[j]) { set_error("%s: grad_state_traj pointer %d is NULL (the reward reads this leaf)", fn, j); return EXCENV_ENULL; }
+    fast_ok = fast_ok && align_of(state_traj[j]) >= 16 && align_of(grad_state_traj[j]) >= 16;
+  }
+  for (int j = 0; j < nc; ++j) {
+    const int64_t sb = ref_strides ? ref_strides[2 * j] : 1, sk = ref_strides ? ref_strides[2 * j + 1] : 0;
+    fast_ok = fast_ok && sb == 1 && (sk == 0 || sk == B) && align_of(control->reference[j]) >= 16;
+  }
+  for (int j = 0; j < t->P; ++j) fast_ok = fast_ok && !props->static_params[j].per_env;
+  for (int j = 0; j < t->S; ++j) fast_ok = fast_ok && !props->state_min[j].per_env && !props->state_max[j].per_env;
+  for (int j = 0; j < t->A; ++j) fast_ok = fast_ok && !props->action_min[j].per_env && !props->action_max[j].per_env;
+  const int V = rew_vjp_envs_per_lane(elem, opts->envs_per_lane, fast_ok);
+  if (V == 0) {
+    set_error("%s: opts.envs_per_lane = %d is not available (1, or %d with lane-major 16-byte aligned arrays, batch_size %% %d == 0 and "
+              "broadcast properties)", fn, opts->envs_per_lane, 16 / elem, 16 / elem);
+    return EXCENV_EINVAL;
+  }
+  for (int j = 0; j < t->S; ++j)  // leaves the reward does not read have a zero cotangent
+    if (!reads[j] && grad_state_traj[j]) {
+      const hipError_t e = hipMemsetAsync(grad_state_traj[j], 0, (size_t)elem * (size_t)rows * (size_t)B, (hipStream_t)stream);
+      if (e != hipSuccess) { set_error("%s: zero-fill of grad_state_traj[%d] failed: %s", fn, j, hipGetErrorString(e)); return EXCENV_EHIP; }
+    }
+  if (!any) {
+    g_last_launch = "rew_vjp_kernel (nothing read: no launch)";
+    return EXCENV_OK;
+  }
+  const RewVjpCall rc{dtype, B, rows, props, control, ref_strides, state_traj, state_env_stride, state_row_stride, grad_reward,
+                      grad_env_stride, grad_row_stride, grad_state_traj, reads, V, stream};
+  return t->rew_vjp(rc);
+}
+
 int excenv_state_from_observation(int env, int dtype, int64_t B, const excenv_props_t* props, int32_t n_control,
                                   const int32_t* control_idx, const void* obs, void* const* state_out,
                                   void* const* reference_out, void* stream) {

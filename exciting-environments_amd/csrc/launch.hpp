@@ -7,6 +7,7 @@
 #include <type_traits>
 #include "kernels_emr.hpp"
 #include "refgen.hpp"
+#include "rew_vjp.hpp"
 #include "vjp.hpp"
 
 namespace excenv {
@@ -132,6 +133,7 @@ struct EnvVTable {
   int (*random_state)(const RandomStateCall&);
   int (*observe)(const ObserveCall&);
   int (*sim_vjp)(const VjpCall&);  // reverse mode of sim (kernels_vjp.hpp)
+  int (*rew_vjp)(const RewVjpCall&);  // reverse mode of traj_gym's reward (kernels_rew_vjp.hpp)
 };
 
 // The reverse-mode launcher of a model: declared here so that it sits in the same table as every other entry point, defined in the
@@ -144,6 +146,15 @@ template <> int vjp_entry<Acrobot>(const VjpCall&);
 template <> int vjp_entry<FluidTank>(const VjpCall&);
 template <> int vjp_entry<Pmsm>(const VjpCall&);
 template <> int vjp_entry<PmsmSat>(const VjpCall&);
+// The transposed reward's launcher, likewise: all seven defined in rew_vjp.hip (the saturated PMSM's is the linear model's)
+template <template <typename> class MT> int rew_vjp_entry(const RewVjpCall&);
+template <> int rew_vjp_entry<Pendulum>(const RewVjpCall&);
+template <> int rew_vjp_entry<MassSpringDamper>(const RewVjpCall&);
+template <> int rew_vjp_entry<CartPole>(const RewVjpCall&);
+template <> int rew_vjp_entry<Acrobot>(const RewVjpCall&);
+template <> int rew_vjp_entry<FluidTank>(const RewVjpCall&);
+template <> int rew_vjp_entry<Pmsm>(const RewVjpCall&);
+template <> int rew_vjp_entry<PmsmSat>(const RewVjpCall&);
 
 template <typename T, class M>
 static bool fill_props(KProps<T, M>& kp, const excenv_props_t* p) {
@@ -684,7 +695,7 @@ template <template <typename> class MT> struct EnvEntry {
   }
   static EnvVTable vtable() {
     return EnvVTable{MT<float>::S, MT<float>::A, MT<float>::O, MT<float>::P, &step, &sim, &traj_gym, &from_obs, &update_ref,
-                     &random_state, &observe, &vjp_entry<MT>};
+                     &random_state, &observe, &vjp_entry<MT>, &rew_vjp_entry<MT>};
   }
 };
 

@@ -943,4 +943,105 @@ __device__ __forceinline__ T env_reward(const T (&st)[M::S], const Ctx<T, M>& c,
   return reward;
 }
 
+// ---- the transposed reward (rew_vjp_kernel, kernels_rew_vjp.hpp) ---------------------------------------------------------------
+// gs[q] += g * d reward / d st[q] at the saved row `st`: the expression trees of pmsm_reward / env_reward above, operation for
+// operation, with the derivative next to every term. Subgradient conventions: the torque reward's derivative is the
+// derivative of the branch the forward selected (the last assignment whose predicate held, the forward's own strict comparisons),
+// 0 where none fired; |x| has derivative sign(x), 0 at 0; i_s = sqrt(i_d^2 + i_q^2) has derivative (i_d, i_q) / i_s, 0 where
+// i_s == 0. References and normalisation bounds get no gradient; NaN propagates as the arithmetic propagates it.
+template <class M, typename T>
+__device__ __forceinline__ void pmsm_reward_vjp(const T (&st)[M::S], const Ctx<T, M>& c, bool has_id, T r_id, bool has_iq, T r_iq,
+                                                bool has_tq, T r_tq, T g, T (&gs)[M::S]) {
+  const T i_d = normalize(st[3], c.smin[3], c.smax[3]);
+  const T i_q = normalize(st[4], c.smin[4], c.smax[4]);
+  T b_id = T(0), b_iq = T(0), b_tq = T(0);  // cotangents of the normalised i_d, i_q, torque
+  if (has_id && has_iq) {  // reward += -1 * ((0.5 dd^2 + 0.5 dq^2) * (1 - 0.85))
+    const T dd = i_d - normalize(r_id, c.smin[3], c.smax[3]);
+    const T dq = i_q - normalize(r_iq, c.smin[4], c.smax[4]);
+    const T gm = (T(-1) * g) * T(1 - 0.85);  // cotangent of mse
+    b_id = b_id + gm * dd;                   // d (0.5 dd^2) = dd
+    b_iq = b_iq + gm * dq;
+  }
+  if (has_tq) {
+    const T tq = normalize(st[5], c.smin[5], c.smax[5]);
+    const T tr = normalize(r_tq, c.smin[5], c.smax[5]);
+    const T i_s = xsqrt(i_d * i_d + i_q * i_q);
+    const T i_n = T(1), i_d_plus = T(0.2) * i_n, tol = T(0.01);
+    // derivative of the selected branch w.r.t. (i_s, i_d, tq): every assignment of the forward overrides all three
+    T d_is = T(0), d_id = T(0), d_tq = T(0);
+    const bool p1 = i_s > T(1);
+    d_is = p1 ? T(-1) * sign_of(i_s) : d_is;  // -1 * |i_s|
+    const bool p2 = (i_s < T(1)) && (i_s > i_n);  // empty for i_n = 1, like the forward's
+    d_is = p2 ? T(-0.5) / (T(1) - i_n) : d_is;
+    const bool p3 = (i_s < i_n) && (i_d > i_d_plus);
+    d_is = p3 ? T(0) : d_is;
+    d_id = p3 ? T(-0.5) / (i_n - i_d_plus) : d_id;
+    const T ad = xabs(tq - tr);
+    const bool p4 = (i_s < i_n) && (i_d < i_d_plus) && (ad > tol);
+    d_is = p4 ? T(0) : d_is;
+    d_id = p4 ? T(0) : d_id;
+    d_tq = p4 ? T(0.5) * (sign_of((tr - tq) / T(2)) / T(2)) : d_tq;  // 0.5 * (1 - |(tr - tq) / 2|): -0.5 * sign(.) * (-1 / 2)
+    const bool p5 = (i_s < i_n) && (i_d < i_d_plus) && (ad < tol);
+    d_is = p5 ? T(-0.5) : d_is;  // 1 - 0.5 * i_s
+    d_id = p5 ? T(0) : d_id;
+    d_tq = p5 ? T(0) : d_tq;
+    const T gw = g * T(1 - 0.85);  // cotangent of rew
+    const T b_is = gw * d_is;
+    const bool origin = i_s == T(0);
+    b_id = b_id + (gw * d_id + (origin ? T(0) : b_is * (i_d / i_s)));
+    b_iq = b_iq + (origin ? T(0) : b_is * (i_q / i_s));
+    b_tq = b_tq + gw * d_tq;
+    gs[5] = gs[5] + b_tq * (T(2) / (c.smax[5] - c.smin[5]));
+  }
+  if ((has_id && has_iq) || has_tq) {  // transpose of normalize: 2 / (hi - lo)
+    gs[3] = gs[3] + b_id * (T(2) / (c.smax[3] - c.smin[3]));
+    gs[4] = gs[4] + b_iq * (T(2) / (c.smax[4] - c.smin[4]));
+  }
+}
+
+template <class M, typename T>
+__device__ __forceinline__ void env_reward_vjp(const T (&st)[M::S], const Ctx<T, M>& c, int n_control, const int* idx,
+                                               const T (&ref)[EXCENV_MAX_CONTROL], T g, T (&gs)[M::S]) {
+  if constexpr (M::IS_PMSM) {
+    T r_id = T(0), r_iq = T(0), r_tq = T(0);
+    bool has_id = false, has_iq = false, has_tq = false;
+#pragma unroll
+    for (int j = 0; j < EXCENV_MAX_CONTROL; ++j) {
+      if (j < n_control) {
+        const int f = idx[j];
+        if (f == 3) { has_id = true; r_id = ref[j]; }
+        if (f == 4) { has_iq = true; r_iq = ref[j]; }
+        if (f == 5) { has_tq = true; r_tq = ref[j]; }
+      }
+    }
+    pmsm_reward_vjp<M, T>(st, c, has_id, r_id, has_iq, r_iq, has_tq, r_tq, g, gs);
+  } else {
+#pragma unroll
+    for (int j = 0; j < EXCENV_MAX_CONTROL; ++j) {
+      if (j < n_control) {
+        const int f = idx[j];
+        T x, lo, hi;
+        pick_field<M, T>(st, c, f, x, lo, hi);
+        const T r = ref[j];
+        bool ang = false;
+#pragma unroll
+        for (int q = 0; q < M::S; ++q) ang = ang || (is_angle_field<M>(q) && f == q);
+        T gx;
+        if (ang) {  // reward += -(ds^2 + dc^2), ds = sin x - sin r, dc = cos x - cos r
+          T sx, cx, sr, cr;
+          sincos_t(x, sx, cx);
+          sincos_t(r, sr, cr);
+          const T ds = sx - sr, dc = cx - cr;
+          gx = -g * (T(2) * (ds * cx) - T(2) * (dc * sx));
+        } else {  // reward += -(d^2), d = normalize(x) - normalize(r)
+          const T d = normalize(x, lo, hi) - normalize(r, lo, hi);
+          gx = (-g * (T(2) * d)) * (T(2) / (hi - lo));
+        }
+#pragma unroll
+        for (int q = 0; q < M::S; ++q) gs[q] = (f == q) ? gs[q] + gx : gs[q];
+      }
+    }
+  }
+}
+
 }  // namespace excenv

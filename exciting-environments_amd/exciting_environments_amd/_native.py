@@ -112,6 +112,10 @@ PROTOTYPES = {
     "excenv_param_grad_sum": (_ci, [_ci, _i64, _i32, _vp, _vp, _vp, _i64, _vp]),
     "excenv_transpose": (_ci, [_ci, _i64, _i64, _vp, _vp, _vp]),
     "excenv_rew_trunc_term": (_ci, [_ci, _ci, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _ci, _vp]),
+    "excenv_rew_reads": (_ci, [_ci, _i32, _vp, _vp]),
+    # env, dtype, B, rows, props, control, ref_strides, state_traj, its two strides, grad_reward, its two strides, grad_state_traj,
+    # opts, stream
+    "excenv_rew_vjp": (_ci, [_ci, _ci, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp]),
     "excenv_state_from_observation": (_ci, [_ci, _ci, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "excenv_update_ref": (_ci, [_ci, _ci, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
     "excenv_observe": (_ci, [_ci, _ci, _i64, _vp, _vp, _vp, _vp, _vp]),
@@ -436,6 +440,24 @@ def rew_trunc_term(env_id, dtype, B, rows, props: Props, control: Optional[Contr
     _launch("excenv_rew_trunc_term", truncated, "vmap_generate_rew_trunc_term_ahead", env_id, dtype_id(dtype), B, rows,
             ctypes.byref(props), _ref(control), rs, _ptrs(state_traj), s_sb, s_sk, reward.data_ptr() if rows > 1 else None,
             terminated.data_ptr() if rows > 1 else None, truncated.data_ptr(), out_layout)
+
+
+def rew_reads(env_id, control_idx: Sequence[int]):
+    """excenv_rew_reads: [bool] per state leaf (MAX_STATE entries) — does the reward with these controlled fields read it?"""
+    reads = (ctypes.c_uint8 * MAX_STATE)()
+    _check(lib().excenv_rew_reads(env_id, len(control_idx), _i32s(control_idx), reads), "excenv_rew_reads")
+    return [bool(r) for r in reads]
+
+
+def rew_vjp(env_id, dtype, B, rows, props: Props, control: Optional[Control], ref_strides: Optional[Sequence[int]],
+            state_traj: Sequence[torch.Tensor], s_sb: int, s_sk: int, grad_reward: Optional[torch.Tensor], g_sb: int, g_sk: int,
+            grad_state_traj: Sequence[Optional[torch.Tensor]], opts: Optional[LaunchOpts] = None):
+    """excenv_rew_vjp: the transposed reward of a stored trajectory; grad_state_traj holds a lane-major [rows, B] tensor per leaf
+    the reward reads (None elsewhere)."""
+    rs = (ctypes.c_int64 * len(ref_strides))(*ref_strides) if ref_strides else None
+    outs = (ctypes.c_void_p * len(grad_state_traj))(*[None if t is None else t.data_ptr() for t in grad_state_traj])
+    _launch("excenv_rew_vjp", state_traj[0], "vmap_reward_vjp", env_id, dtype_id(dtype), B, rows, ctypes.byref(props), _ref(control),
+            rs, _ptrs(state_traj), s_sb, s_sk, _ptr(grad_reward) if rows > 1 else None, g_sb, g_sk, outs, _ref(opts))
 
 
 def state_from_observation(env_id, dtype, B, props: Props, control_idx: Sequence[int], obs: torch.Tensor,

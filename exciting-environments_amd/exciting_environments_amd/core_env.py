@@ -28,6 +28,7 @@ from ._native import cuda_get_device as _cuda_get_device, cuda_is_capturing as _
 from . import random as _random
 from ._placement import StepSlotPool, TrajectoryPlacement
 from ._trajectory import TrajectoryLaunchMixin
+from ._reward_vjp import RewardVjpMixin
 from ._vjp import TrajectoryVjpMixin
 from .solvers import Euler, _Solver
 from .tree import tree_structure
@@ -43,7 +44,7 @@ def _is_scalar(x) -> bool:
     return _is_array(x) and x.ndim == 0
 
 
-class CoreEnvironment(TrajectoryLaunchMixin, TrajectoryVjpMixin, ABC):
+class CoreEnvironment(TrajectoryLaunchMixin, TrajectoryVjpMixin, RewardVjpMixin, ABC):
     """Core structure of the provided environments (reference core_env.py:15-57).
 
     The simulated systems are physical state-space models dx/dt = f(x(t), u(t)); outputs are
@@ -688,7 +689,12 @@ class CoreEnvironment(TrajectoryLaunchMixin, TrajectoryVjpMixin, ABC):
         """core_env.py:618-647 / :490-531 for trajectories returned by vmap_sim_ahead: reward [B,K,1] on rows 1..,
         truncated [B,K+1,TW] on all rows, terminated [B,K,1] on rows 1... One HIP launch over the stored trajectory
         (excenv_rew_trunc_term; `vmap_sim_ahead(..., return_rew_trunc_term=True)` produces the same values inside the
-        trajectory launch itself). CPU tensors fall back to the elementwise torch mirror."""
+        trajectory launch itself). CPU tensors fall back to the elementwise torch mirror.
+
+        With `env.differentiable` set, grad mode on and a physical-state leaf of `states` that requires grad (the states of a
+        differentiable vmap_sim_ahead call), the same launch is recorded as one autograd node: the reward carries a graph whose
+        backward is one excenv_rew_vjp launch (vmap_reward_vjp); truncated and terminated never do. Nothing is recorded when no
+        controlled field makes the reward depend on the state."""
         actions = torch.as_tensor(actions)
         assert actions.ndim == 3, "The actions need to have three dimensions: (batch_size, n_action_steps, action_dim)"
         assert (
@@ -699,33 +705,53 @@ class CoreEnvironment(TrajectoryLaunchMixin, TrajectoryVjpMixin, ABC):
         ), f"The last dimension does not correspond to the action dim which is {self.action_dim}, but {actions.shape[-1]} is given"
         leaves = [torch.as_tensor(getattr(states.physical_state, n)) for n in self.STATE_FIELDS]
         if leaves[0].is_cuda and leaves[0].ndim == 2 and leaves[0].shape[0] == self.batch_size:
+            if self._reward_wants_grad(leaves):  # env.differentiable and a state leaf requires grad: one autograd node (_reward_vjp.py)
+                return self._rew_trunc_term_differentiable(states, leaves)
             return self._rew_trunc_term_device(states, leaves)
         return self._rew_trunc_term_torch(states)
 
-    def _rew_trunc_term_device(self, states, leaves):
+    def _rew_leaves(self, leaves):
+        """The [B, rows] state leaves as a launch over a stored trajectory reads them: working dtype, one common pair of strides."""
         B, rows = leaves[0].shape
-        N = rows - 1
         leaves = [l if (l.dtype == self.dtype and l.device == self.device) else l.to(device=self.device, dtype=self.dtype)
                   for l in leaves]
         strides = {tuple(l.stride()) for l in leaves}
         if len(strides) != 1 or any(l.shape != (B, rows) for l in leaves):
             leaves = [l.contiguous() for l in leaves]
+        return leaves
+
+    def _rew_refs(self, reference, B, rows):
+        """[B, rows] views of the controlled fields' references (broadcast along the rows where they are [B] leaves)."""
+        refs = []
+        for n in self.control_state:
+            r = torch.as_tensor(getattr(reference, n))
+            if not (r.is_cuda and r.dtype == self.dtype):
+                r = r.to(device=self.device, dtype=self.dtype)
+            if r.ndim != 2 or tuple(r.shape) != (B, rows):
+                r = r.reshape(B, -1).expand(B, rows) if r.ndim >= 1 else r.expand(B, rows)
+            refs.append(r)
+        return refs
+
+    def _rew_control(self, refs):
+        """excenv_control_t and the (env, row) element strides of the references of `_rew_refs`"""
+        if not self.control_state:
+            return None, None
+        idx = [self.STATE_FIELDS.index(n) for n in self.control_state]
+        ref_strides = []
+        for r in refs:
+            ref_strides += list(r.stride())
+        return _native.make_control(idx, refs), ref_strides
+
+    def _rew_trunc_term_device(self, states, leaves, packed=None, refs=None):
+        B, rows = leaves[0].shape
+        N = rows - 1
+        leaves = self._rew_leaves(leaves)
         s_sb, s_sk = leaves[0].stride()
         lane_major = (s_sb == 1 and rows > 1)
-        props, keep = self._props_for(self.env_properties, B)
-        control, ref_strides, refs = None, None, []
-        if self.control_state:
-            idx = [self.STATE_FIELDS.index(n) for n in self.control_state]
-            ref_strides = []
-            for n in self.control_state:
-                r = torch.as_tensor(getattr(states.reference, n))
-                if not (r.is_cuda and r.dtype == self.dtype):
-                    r = r.to(device=self.device, dtype=self.dtype)
-                if r.ndim != 2 or tuple(r.shape) != (B, rows):
-                    r = r.reshape(B, -1).expand(B, rows) if r.ndim >= 1 else r.expand(B, rows)
-                refs.append(r)
-                ref_strides += list(r.stride())
-            control = _native.make_control(idx, refs)
+        props, keep = packed if packed is not None else self._props_for(self.env_properties, B)
+        if refs is None:
+            refs = self._rew_refs(states.reference, B, rows)
+        control, ref_strides = self._rew_control(refs)
         TW = _native.truncated_width(self.ENV_ID, len(self.control_state))
         if lane_major:  # outputs as [B, ., .] views over lane-major memory, like the trajectories themselves
             rew_buf = torch.empty((max(N, 0), B), dtype=self.dtype, device=self.device)
@@ -924,6 +950,8 @@ class CoreEnvironment(TrajectoryLaunchMixin, TrajectoryVjpMixin, ABC):
         )
         B = self.batch_size
         if self._wants_grad(init_state, actions):  # env.differentiable and something requires grad: one autograd node (_vjp.py)
+            # the fused gym outputs stay refused here: the supported route to a differentiable reward is the two-call composition
+            # vmap_sim_ahead(...) -> vmap_generate_rew_trunc_term_ahead(states, actions), whose reward then carries a graph
             if out is not None or return_rew_trunc_term:
                 raise ValueError("vmap_sim_ahead: a differentiable call cannot be combined with out= or return_rew_trunc_term=True "
                                  "(their outputs have no reverse mode); detach the inputs or set env.differentiable = False")

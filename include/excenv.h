@@ -355,6 +355,33 @@ int excenv_rew_trunc_term(int env, int dtype, int64_t B, int64_t rows, const exc
                           int64_t state_env_stride, int64_t state_row_stride, void* reward, uint8_t* terminated,
                           uint8_t* truncated, int out_layout, void* stream);
 
+/* ---- reverse mode of the reward above (what jax.grad gives through the reference's generate_reward; additions, same ABI
+ * version: a binder probes for the symbols). The reward of row n depends on the state of row n only: one launch of
+ * rew_vjp_kernel evaluates the transposed reward at every saved row and writes the cotangents of the state leaves the reward reads,
+ * in the layout excenv_sim_ahead_vjp takes as grad_state_traj.
+ * excenv_rew_reads (host only): reads[j] = 1 where the reward reads state leaf j, else 0 — the controlled fields; PMSM: i_d and
+ * i_q when both are controlled, i_d, i_q and torque when torque is controlled, nothing otherwise. EXCENV_EINVAL for a bad env,
+ * n_control or index, EXCENV_ENULL for a NULL array.
+ * excenv_rew_vjp: props, control, ref_strides, state_traj and its two strides as for excenv_rew_trunc_term (state_traj[j] may
+ * be NULL for a leaf that is not read; per-environment property arrays and the saturated PMSM are accepted, the reward does not
+ * depend on the look-up tables), then
+ *   grad_reward     : cotangent of the reward, rows-1 values per env (row n >= 1 at index n-1) with element strides
+ *                     (grad_env_stride, grad_row_stride); may be NULL when rows == 1
+ *   grad_state_traj : S pointers (out), lane-major [rows][B] each. Row 0 is written as zeros (the reward covers rows 1..). NULL for
+ *                     a leaf that is read: EXCENV_ENULL, naming the leaf; a non-NULL array of a leaf that is not read is zero-filled.
+ * Two forms with the same bits; excenv_last_launch() names the one that ran: "rew_vjp_kernel (V=2|V=4)", 16 bytes per lane, when
+ * the state leaves are lane-major (strides (1, B)), B % (16 / sizeof(dtype)) == 0, every array is 16-byte aligned, each reference
+ * is constant along rows (strides (1, 0)) or lane-major, grad_reward is lane-major and no property is a per-environment array;
+ * "rew_vjp_kernel (V=1, strided)", one element per lane, otherwise. opts->envs_per_lane: 0 = that rule, 1 or 16 / sizeof(dtype) =
+ * forced (a width that cannot be had: EXCENV_EINVAL). B == 0 returns EXCENV_OK without a launch, rows == 1 writes the zero row only.
+ * Subgradients: the torque reward's derivative is that of the branch the forward selected (0 where none fired), |x| has derivative
+ * sign(x) (0 at 0), sqrt(i_d^2 + i_q^2) has derivative 0 at the origin. References and normalisation bounds get no gradient. */
+int excenv_rew_reads(int env, int32_t n_control, const int32_t* control_idx, uint8_t reads[EXCENV_MAX_STATE]);
+int excenv_rew_vjp(int env, int dtype, int64_t B, int64_t rows, const excenv_props_t* props,
+                   const excenv_control_t* control, const int64_t* ref_strides, const void* const* state_traj,
+                   int64_t state_env_stride, int64_t state_row_stride, const void* grad_reward, int64_t grad_env_stride,
+                   int64_t grad_row_stride, void* const* grad_state_traj, const excenv_launch_opts_t* opts, void* stream);
+
 /* ---- replaces CoreEnvironment.vmap_generate_state_from_observation (core_env.py:689-705; per env e.g.
  * pendulum_env.py:331-364, pmsm_env.py:921-970): obs [B][O + n_control] row-major -> denormalised physical state leaves
  * state_out[S][B] and, for each controlled field control_idx[j], its denormalised reference leaf reference_out[j][B]
