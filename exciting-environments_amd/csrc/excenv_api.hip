@@ -537,6 +537,67 @@ int excenv_rew_vjp(int env, int dtype, int64_t B, int64_t rows, const excenv_pro
   return t->rew_vjp(rc);
 }
 
+int64_t excenv_step_vjp_bytes(int env, int dtype, int32_t n_control, int has_grad_obs, int has_grad_state, int has_grad_reward) {
+  const EnvVTable* t = table_public(env);
+  if (!t || (dtype != EXCENV_F32 && dtype != EXCENV_F64) || n_control < 0 || n_control > EXCENV_MAX_CONTROL) return -1;
+  return step_vjp_bytes(t->S, t->A, t->O, dtype == EXCENV_F64 ? 8 : 4, n_control, has_grad_obs != 0, has_grad_state != 0, has_grad_reward != 0);
+}
+
+int excenv_step_vjp(int env, int solver, int dtype, int64_t B, const excenv_props_t* props, const excenv_control_t* control,
+                    double tau, const void* const* state_in, const void* action, const void* const* state_out,
+                    const void* grad_obs, const void* const* grad_state_out, const void* grad_reward,
+                    void* const* grad_state_in, void* grad_action, const excenv_launch_opts_t* opts, void* stream) {
+  const char* fn = "excenv_step_vjp";
+  if (int rc = check_common(fn, env, solver, dtype, B)) return rc;
+  if (!props) { set_error("%s: props is NULL", fn); return EXCENV_ENULL; }
+  if (props->pmsm_lut) { set_error("%s: the saturated PMSM (pmsm_lut) has no reverse mode", fn); return EXCENV_EUNSUPPORTED; }
+  const EnvVTable* t = table_public(env);
+  if (control && control->n_control == 0) control = nullptr;
+  const int nc = control ? control->n_control : 0;
+  if (nc < 0 || nc > EXCENV_MAX_CONTROL) { set_error("%s: bad n_control %d", fn, nc); return EXCENV_EINVAL; }
+  if (grad_reward) {  // the reward reads the controlled fields and their references; without any it is a constant
+    if (!control) {
+      set_error("%s: grad_reward without control references (the reward depends on the state through the controlled fields only)", fn);
+      return EXCENV_EUNSUPPORTED;
+    }
+    for (int j = 0; j < nc; ++j) {
+      if (control->control_idx[j] < 0 || control->control_idx[j] >= t->S) { set_error("%s: control_idx[%d] out of range", fn, j); return EXCENV_EINVAL; }
+      if (!control->reference[j]) { set_error("%s: reference[%d] is NULL (grad_reward reads the references)", fn, j); return EXCENV_ENULL; }
+    }
+  }
+  if (int rc = check_opts(fn, opts)) return rc;
+  {
+    bool per_env = false;
+    for (int j = 0; j < t->P; ++j) per_env |= props->static_params[j].per_env != nullptr;
+    for (int j = 0; j < t->S; ++j) per_env |= props->state_min[j].per_env != nullptr || props->state_max[j].per_env != nullptr;
+    for (int j = 0; j < t->A; ++j) per_env |= props->action_min[j].per_env != nullptr || props->action_max[j].per_env != nullptr;
+    if (per_env) { set_error("%s: per-environment property arrays are not supported (broadcast properties only)", fn); return EXCENV_EUNSUPPORTED; }
+  }
+  if (B == 0) return EXCENV_OK;  // nothing to write: no launch, whatever the (empty) arrays' addresses are
+  if (!state_in) { set_error("%s: state_in is NULL", fn); return EXCENV_ENULL; }
+  if (!action) { set_error("%s: action is NULL", fn); return EXCENV_ENULL; }
+  if (!state_out) { set_error("%s: state_out is NULL", fn); return EXCENV_ENULL; }
+  if (!grad_state_in) { set_error("%s: grad_state_in is NULL", fn); return EXCENV_ENULL; }
+  if (!grad_action) { set_error("%s: grad_action is NULL", fn); return EXCENV_ENULL; }
+  for (int j = 0; j < t->S; ++j) {
+    if (!state_in[j]) { set_error("%s: state_in pointer %d is NULL", fn, j); return EXCENV_ENULL; }
+    if (!state_out[j]) { set_error("%s: state_out pointer %d is NULL", fn, j); return EXCENV_ENULL; }
+    if (!grad_state_in[j]) { set_error("%s: grad_state_in pointer %d is NULL", fn, j); return EXCENV_ENULL; }
+  }
+  const int V = step_vjp_envs_per_lane(opts->envs_per_lane);
+  if (V == 0) {
+    set_error("%s: opts.envs_per_lane = %d is not available (this kernel has the one-environment-per-lane form only)", fn, opts->envs_per_lane);
+    return EXCENV_EINVAL;
+  }
+  if (align_of(action) < 16 || align_of(grad_action) < 16 || align_of(grad_obs) < 16) {  // rows are read as 16-byte pieces
+    set_error("%s: action, grad_action and grad_obs must be 16-byte aligned", fn);
+    return EXCENV_EINVAL;
+  }
+  const StepVjpCall sc{solver, dtype, B, props, control, tau, state_in, action, state_out, grad_obs, grad_state_out, grad_reward,
+                       grad_state_in, grad_action, V, stream};
+  return t->step_vjp(sc);
+}
+
 int excenv_state_from_observation(int env, int dtype, int64_t B, const excenv_props_t* props, int32_t n_control,
                                   const int32_t* control_idx, const void* obs, void* const* state_out,
                                   void* const* reference_out, void* stream) {

@@ -116,6 +116,10 @@ PROTOTYPES = {
     # env, dtype, B, rows, props, control, ref_strides, state_traj, its two strides, grad_reward, its two strides, grad_state_traj,
     # opts, stream
     "excenv_rew_vjp": (_ci, [_ci, _ci, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp]),
+    # env, solver, dtype, B, props, control, tau, state_in, action, state_out, grad_obs, grad_state_out, grad_reward, grad_state_in,
+    # grad_action, opts, stream
+    "excenv_step_vjp": (_ci, [_ci, _ci, _ci, _i64, _vp, _vp, _cd, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "excenv_step_vjp_bytes": (_i64, [_ci, _ci, _i32, _ci, _ci, _ci]),
     "excenv_state_from_observation": (_ci, [_ci, _ci, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "excenv_update_ref": (_ci, [_ci, _ci, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
     "excenv_observe": (_ci, [_ci, _ci, _i64, _vp, _vp, _vp, _vp, _vp]),
@@ -458,6 +462,12 @@ def rew_vjp(env_id, dtype, B, rows, props: Props, control: Optional[Control], re
     outs = (ctypes.c_void_p * len(grad_state_traj))(*[None if t is None else t.data_ptr() for t in grad_state_traj])
     _launch("excenv_rew_vjp", state_traj[0], "vmap_reward_vjp", env_id, dtype_id(dtype), B, rows, ctypes.byref(props), _ref(control),
             rs, _ptrs(state_traj), s_sb, s_sk, _ptr(grad_reward) if rows > 1 else None, g_sb, g_sk, outs, _ref(opts))
+
+
+def step_vjp_bytes(env_id: int, dtype: torch.dtype, n_control: int = 0, grad_obs: bool = True, grad_state: bool = True,
+                   grad_reward: bool = False) -> int:
+    """excenv_step_vjp_bytes: the algorithmic bytes per environment of one excenv_step_vjp launch with these cotangent groups."""
+    return lib().excenv_step_vjp_bytes(env_id, dtype_id(dtype), n_control, int(grad_obs), int(grad_state), int(grad_reward))
 
 
 def state_from_observation(env_id, dtype, B, props: Props, control_idx: Sequence[int], obs: torch.Tensor,

@@ -87,7 +87,9 @@ class TrajectoryVjpMixin:
         """False (default): vmap_sim_ahead returns plain tensors, exactly as without this property. True: when grad mode is on
         and the actions or a leaf of the initial physical state require grad, the call records one autograd node whose backward
         is the reverse-mode kernel (the state trajectory is always produced then; not combinable with out=,
-        return_rew_trunc_term=True or anything vmap_sim_ahead_vjp rejects)."""
+        return_rew_trunc_term=True or anything vmap_sim_ahead_vjp rejects). The same switch makes vmap_step / vmap_gym_step
+        (an action or physical-state leaf that requires grad; _step_vjp.py) and the reward of
+        vmap_generate_rew_trunc_term_ahead (_reward_vjp.py) record their nodes."""
         return getattr(self, "_differentiable", False)
 
     @differentiable.setter

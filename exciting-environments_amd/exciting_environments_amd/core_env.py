@@ -29,6 +29,7 @@ from . import random as _random
 from ._placement import StepSlotPool, TrajectoryPlacement
 from ._trajectory import TrajectoryLaunchMixin
 from ._reward_vjp import RewardVjpMixin
+from ._step_vjp import StepVjpMixin
 from ._vjp import TrajectoryVjpMixin
 from .solvers import Euler, _Solver
 from .tree import tree_structure
@@ -44,7 +45,7 @@ def _is_scalar(x) -> bool:
     return _is_array(x) and x.ndim == 0
 
 
-class CoreEnvironment(TrajectoryLaunchMixin, TrajectoryVjpMixin, RewardVjpMixin, ABC):
+class CoreEnvironment(TrajectoryLaunchMixin, TrajectoryVjpMixin, RewardVjpMixin, StepVjpMixin, ABC):
     """Core structure of the provided environments (reference core_env.py:15-57).
 
     The simulated systems are physical state-space models dx/dt = f(x(t), u(t)); outputs are
@@ -118,7 +119,8 @@ class CoreEnvironment(TrajectoryLaunchMixin, TrajectoryVjpMixin, RewardVjpMixin,
         self.store_state_trajectory = True
         # per-call launch options (excenv_launch_opts_t); None = library defaults. Tuning experiments only.
         self.launch_opts = None
-        # True: vmap_sim_ahead records an autograd node when a gradient is asked for (_vjp.py); False: plain tensors, as ever
+        # True: vmap_sim_ahead (_vjp.py), vmap_step and vmap_gym_step (_step_vjp.py) record an autograd node when a gradient is asked
+        # for; False: plain tensors, as ever
         self.differentiable = False
         self._packed_props = None
         self._packed_for = None
@@ -612,25 +614,36 @@ class CoreEnvironment(TrajectoryLaunchMixin, TrajectoryVjpMixin, RewardVjpMixin,
         return sl.obs[i], new_state
 
     def vmap_step(self, state, action):
-        """One simulation step of all batch_size environments (core_env.py:533-569): one fused HIP launch."""
+        """One simulation step of all batch_size environments (core_env.py:533-569): one fused HIP launch.
+
+        With `env.differentiable` set, grad mode on and an action or a physical-state leaf that requires grad, the same launch is
+        recorded as one autograd node whose backward is one excenv_step_vjp launch (_step_vjp.py, `vmap_step_vjp`): the closed
+        loop `action = policy(obs)` differentiates through every step. In every other case nothing is recorded."""
         if type(action) is not torch.Tensor:
             action = torch.as_tensor(action)
         assert action.shape == (self.batch_size, self.action_dim), (
             "The action needs to be of shape (batch_size, action_dim) which is "
             + f"{(self.batch_size, self.action_dim)}, but {tuple(action.shape)} is given"
         )
+        if self._differentiable and self._step_wants_grad(state, action):
+            return self._step_differentiable(state, action, False)
         return self._vmap_step_launch(state, action, False)
 
     def vmap_gym_step(self, state, action):
         """vmap_step fused with generate_reward / generate_terminated / generate_truncated in ONE launch — what
         GymWrapper.gym_step computes per step (gym_wrapper.py:88-130). Returns
-        (obs [B,O], reward [B,1], terminated [B,1] bool, truncated [B,TW] bool, new_state)."""
+        (obs [B,O], reward [B,1], terminated [B,1] bool, truncated [B,TW] bool, new_state).
+
+        Differentiable under the conditions of `vmap_step`: obs, reward and the new state then carry a graph (one node, one
+        excenv_step_vjp launch in backward, the reward's transpose included); terminated and truncated never do."""
         if type(action) is not torch.Tensor:
             action = torch.as_tensor(action)
         assert action.shape == (self.batch_size, self.action_dim), (
             "The action needs to be of shape (batch_size, action_dim) which is "
             + f"{(self.batch_size, self.action_dim)}, but {tuple(action.shape)} is given"
         )
+        if self._differentiable and self._step_wants_grad(state, action):
+            return self._step_differentiable(state, action, True)
         return self._vmap_step_launch(state, action, True)
 
     # ------------------------------------------------------------------ reward / truncated / terminated (torch mirrors)

@@ -49,7 +49,7 @@ class GymWrapper:
 
     def step(self, action):
         """One simulation step (gym_wrapper.py:67-86): observation [B,obs_dim], reward [B,1], terminated [B,1],
-        truncated [B, n_flags]."""
+        truncated [B, n_flags]. Graph-free whatever `env.differentiable` says (see gym_step)."""
         obs, reward, terminated, truncated, self.state, self.reference_hold_steps = self.gym_step(
             action, self.state, self.reference_hold_steps
         )
@@ -64,8 +64,14 @@ class GymWrapper:
         the host (one device read whenever references were redrawn): while it is positive no environment can be due, the
         step is the single fused launch (`excenv_gym_step`) and the counters are decremented; when it reaches zero the step
         takes the literal path. Same results either way (`test_gym_wrapper_ref_generation_fast_path_equals_literal_path`).
-        The mirror is used only for the wrapper's own counter tensor (`step()`); foreign counters take the literal path."""
+        The mirror is used only for the wrapper's own counter tensor (`step()`); foreign counters take the literal path.
+
+        The outputs never carry an autograd graph, whatever `env.differentiable` says: the wrapper's reset and reference logic
+        writes states in place. A differentiable closed loop calls `env.vmap_gym_step` itself."""
         env = self.env
+        if env.differentiable and torch.is_grad_enabled():
+            with torch.no_grad():
+                return self.gym_step(action, state, reference_hold_steps)
         custom = self.generate_reward or self.generate_terminated or self.generate_truncated
         regen = len(self.control_state) and self.ref_gen
         if not custom and not regen:

@@ -382,6 +382,30 @@ int excenv_rew_vjp(int env, int dtype, int64_t B, int64_t rows, const excenv_pro
                    int64_t state_env_stride, int64_t state_row_stride, const void* grad_reward, int64_t grad_env_stride,
                    int64_t grad_row_stride, void* const* grad_state_traj, const excenv_launch_opts_t* opts, void* stream);
 
+/* ---- reverse mode of ONE excenv_step / excenv_gym_step call (what jax.grad gives through the reference's vmap_step inside a closed
+ * loop, where the action of step n is a function of the observation of step n; additions, same ABI version: a binder probes for the
+ * symbols). One launch of step_vjp_kernel, one lane per environment, the arithmetic of a row of excenv_sim_ahead_vjp under
+ * EXCENV_SEM_STEP with the transposed reward folded in:
+ *   state_in, action  : what the forward call was handed (S x [B]; row-major [B][A], 16-byte aligned)
+ *   state_out         : S x [B], the state the forward call returned. It is read as the post-processed state, not recomputed.
+ *   grad_obs          : cotangent of obs, row-major [B][O + n_control] (control->n_control; 16-byte aligned), or NULL. The control
+ *                       columns are skipped: references get no gradient.
+ *   grad_state_out    : NULL, or S pointers ([B] or NULL each): cotangent of the returned state
+ *   grad_reward       : cotangent of excenv_gym_step's reward, [B], or NULL. With it `control` carries the controlled fields and
+ *                       their [B] references (control->reference; obs_reference is not read); without it only n_control is read.
+ *   grad_state_in     : S x [B] (out), grad_action: row-major [B][A] (out, 16-byte aligned)
+ * Never allocates or synchronises; graph-capturable. B == 0 returns EXCENV_OK without a launch. excenv_last_launch() names the
+ * form: "step_vjp_kernel (V=1)", the only one (opts->envs_per_lane other than 0 or 1: EXCENV_EINVAL). EXCENV_ENULL names a missing
+ * required pointer. EXCENV_EUNSUPPORTED: the saturated PMSM (pmsm_lut), per-environment property arrays, a grad_reward without
+ * control references. Subgradient conventions as excenv_sim_ahead_vjp and excenv_rew_vjp.
+ * excenv_step_vjp_bytes (host only): the algorithmic bytes per environment, w (2S + A) in, plus w (O + n_control) with grad_obs,
+ * w S with a state cotangent, w (1 + n_control) with grad_reward, and w (S + A) out; -1 for a bad argument. */
+int excenv_step_vjp(int env, int solver, int dtype, int64_t B, const excenv_props_t* props, const excenv_control_t* control,
+                    double tau, const void* const* state_in, const void* action, const void* const* state_out,
+                    const void* grad_obs, const void* const* grad_state_out, const void* grad_reward,
+                    void* const* grad_state_in, void* grad_action, const excenv_launch_opts_t* opts, void* stream);
+int64_t excenv_step_vjp_bytes(int env, int dtype, int32_t n_control, int has_grad_obs, int has_grad_state, int has_grad_reward);
+
 /* ---- replaces CoreEnvironment.vmap_generate_state_from_observation (core_env.py:689-705; per env e.g.
  * pendulum_env.py:331-364, pmsm_env.py:921-970): obs [B][O + n_control] row-major -> denormalised physical state leaves
  * state_out[S][B] and, for each controlled field control_idx[j], its denormalised reference leaf reference_out[j][B]

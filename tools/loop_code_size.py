@@ -24,8 +24,9 @@ OBJDUMP = "/opt/rocm/lib/llvm/bin/llvm-objdump"
 HEADLINE = "_ZN6excenv16sim_ahead_kernelINS_4PmsmIfEEfLi0ELb1ELb0ELi4ELi1ELb0ELb0ELb0ELi256EEEvNS_7SimArgsIT0_T_EE"
 
 
-def loop_spans(lib=LIB):
-    """{kernel symbol: (largest backward-branch span in bytes, kernel size in bytes)} for the trajectory kernels."""
+def loop_spans(lib=LIB, match="sim_ahead"):
+    """{kernel symbol: (largest backward-branch span in bytes, kernel size in bytes)} for the kernels whose symbol contains `match`
+    (default: the trajectory kernels). A kernel without a loop has span 0."""
     out = {}
     with tempfile.TemporaryDirectory() as td:
         so = os.path.join(td, "lib.so")
@@ -37,7 +38,7 @@ def loop_spans(lib=LIB):
             for line in dis.splitlines():
                 m = re.match(r"^([0-9a-f]+) <(\S+)>:", line)
                 if m:
-                    if sym and "sim_ahead" in sym:
+                    if sym and match in sym:
                         out[sym] = (span, last - first)
                     sym, first, last, span = m.group(2), int(m.group(1), 16), int(m.group(1), 16), 0
                     continue
@@ -52,7 +53,7 @@ def loop_spans(lib=LIB):
                         target = first + int(t.group(1), 16)
                         if target <= addr:
                             span = max(span, addr - target)
-            if sym and "sim_ahead" in sym:
+            if sym and match in sym:
                 out[sym] = (span, last - first)
     return out
 
