@@ -598,6 +598,56 @@ int excenv_step_vjp(int env, int solver, int dtype, int64_t B, const excenv_prop
   return t->step_vjp(sc);
 }
 
+int64_t excenv_step_jacobian_bytes(int env, int dtype, int row_kind) {
+  const EnvVTable* t = table_public(env);
+  if (!t || (dtype != EXCENV_F32 && dtype != EXCENV_F64) || (row_kind != EXCENV_JAC_STATE && row_kind != EXCENV_JAC_OBS)) return -1;
+  return step_jac_bytes(t->S, t->A, t->O, dtype == EXCENV_F64 ? 8 : 4, row_kind);
+}
+
+int excenv_step_jacobian(int env, int solver, int dtype, int64_t B, int64_t rows, int32_t substeps, const excenv_props_t* props,
+                         int32_t n_control, double dt, double env_tau, const void* const* state_in, const void* const* state_out,
+                         int64_t state_row_stride, const void* action, int64_t action_row_stride, int64_t action_comp_stride,
+                         int64_t action_env_stride, int row_kind, void* jacobian, const excenv_launch_opts_t* opts, void* stream) {
+  const char* fn = "excenv_step_jacobian";
+  if (int rc = check_common(fn, env, solver, dtype, B)) return rc;
+  if (rows < 0) { set_error("%s: bad rows %lld", fn, (long long)rows); return EXCENV_EINVAL; }
+  if (substeps < 1) { set_error("%s: bad substeps %d (at least 1)", fn, (int)substeps); return EXCENV_EINVAL; }
+  if (n_control < 0 || n_control > EXCENV_MAX_CONTROL) { set_error("%s: bad n_control %d", fn, (int)n_control); return EXCENV_EINVAL; }
+  if (row_kind != EXCENV_JAC_STATE && row_kind != EXCENV_JAC_OBS) { set_error("%s: bad row_kind %d", fn, row_kind); return EXCENV_EINVAL; }
+  if (!props) { set_error("%s: props is NULL", fn); return EXCENV_ENULL; }
+  if (props->pmsm_lut) { set_error("%s: the saturated PMSM (pmsm_lut) has no reverse mode", fn); return EXCENV_EUNSUPPORTED; }
+  const EnvVTable* t = table_public(env);
+  if (int rc = check_opts(fn, opts)) return rc;
+  {
+    bool per_env = false;
+    for (int j = 0; j < t->P; ++j) per_env |= props->static_params[j].per_env != nullptr;
+    for (int j = 0; j < t->S; ++j) per_env |= props->state_min[j].per_env != nullptr || props->state_max[j].per_env != nullptr;
+    for (int j = 0; j < t->A; ++j) per_env |= props->action_min[j].per_env != nullptr || props->action_max[j].per_env != nullptr;
+    if (per_env) { set_error("%s: per-environment property arrays are not supported (broadcast properties only)", fn); return EXCENV_EUNSUPPORTED; }
+  }
+  const int V = step_jac_envs_per_lane(opts->envs_per_lane);
+  if (V == 0) {
+    set_error("%s: opts.envs_per_lane = %d is not available (this kernel has the one-instance-per-lane form only)", fn, opts->envs_per_lane);
+    return EXCENV_EINVAL;
+  }
+  if (B == 0 || rows == 0) return EXCENV_OK;  // nothing to write: no launch, whatever the (empty) arrays' addresses are
+  if (!state_in) { set_error("%s: state_in is NULL", fn); return EXCENV_ENULL; }
+  if (!state_out) { set_error("%s: state_out is NULL", fn); return EXCENV_ENULL; }
+  if (!action) { set_error("%s: action is NULL", fn); return EXCENV_ENULL; }
+  if (!jacobian) { set_error("%s: jacobian is NULL", fn); return EXCENV_ENULL; }
+  for (int j = 0; j < t->S; ++j) {
+    if (!state_in[j]) { set_error("%s: state_in pointer %d is NULL", fn, j); return EXCENV_ENULL; }
+    if (!state_out[j]) { set_error("%s: state_out pointer %d is NULL", fn, j); return EXCENV_ENULL; }
+  }
+  if (state_row_stride < 0 || action_row_stride < 0 || action_comp_stride < 0 || action_env_stride < 0) {
+    set_error("%s: strides must not be negative", fn);
+    return EXCENV_EINVAL;
+  }
+  const StepJacCall jc{solver, dtype, B, rows, substeps, props, dt, env_tau, state_in, state_out, state_row_stride, action,
+                       action_row_stride, action_comp_stride, action_env_stride, row_kind, jacobian, V, stream};
+  return t->step_jac(jc);
+}
+
 int excenv_state_from_observation(int env, int dtype, int64_t B, const excenv_props_t* props, int32_t n_control,
                                   const int32_t* control_idx, const void* obs, void* const* state_out,
                                   void* const* reference_out, void* stream) {

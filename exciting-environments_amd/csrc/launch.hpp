@@ -8,6 +8,7 @@
 #include "kernels_emr.hpp"
 #include "refgen.hpp"
 #include "rew_vjp.hpp"
+#include "step_jac.hpp"
 #include "step_vjp.hpp"
 #include "vjp.hpp"
 
@@ -136,6 +137,7 @@ struct EnvVTable {
   int (*sim_vjp)(const VjpCall&);  // reverse mode of sim (kernels_vjp.hpp)
   int (*rew_vjp)(const RewVjpCall&);  // reverse mode of traj_gym's reward (kernels_rew_vjp.hpp)
   int (*step_vjp)(const StepVjpCall&);  // reverse mode of step (kernels_step_vjp.hpp)
+  int (*step_jac)(const StepJacCall&);  // Jacobians of step, row by row (kernels_step_jac.hpp)
 };
 
 // The reverse-mode launcher of a model: declared here so that it sits in the same table as every other entry point, defined in the
@@ -168,6 +170,17 @@ template <> int step_vjp_entry<Acrobot>(const StepVjpCall&);
 template <> int step_vjp_entry<FluidTank>(const StepVjpCall&);
 template <> int step_vjp_entry<Pmsm>(const StepVjpCall&);
 template <> int step_vjp_entry<PmsmSat>(const StepVjpCall&);
+
+// The step Jacobian launcher, likewise: defined in the model's own translation unit step_jac_<model>.hip (the saturated PMSM's
+// reports that it has none)
+template <template <typename> class MT> int step_jac_entry(const StepJacCall&);
+template <> int step_jac_entry<Pendulum>(const StepJacCall&);
+template <> int step_jac_entry<MassSpringDamper>(const StepJacCall&);
+template <> int step_jac_entry<CartPole>(const StepJacCall&);
+template <> int step_jac_entry<Acrobot>(const StepJacCall&);
+template <> int step_jac_entry<FluidTank>(const StepJacCall&);
+template <> int step_jac_entry<Pmsm>(const StepJacCall&);
+template <> int step_jac_entry<PmsmSat>(const StepJacCall&);
 
 template <typename T, class M>
 static bool fill_props(KProps<T, M>& kp, const excenv_props_t* p) {
@@ -708,7 +721,7 @@ template <template <typename> class MT> struct EnvEntry {
   }
   static EnvVTable vtable() {
     return EnvVTable{MT<float>::S, MT<float>::A, MT<float>::O, MT<float>::P, &step, &sim, &traj_gym, &from_obs, &update_ref,
-                     &random_state, &observe, &vjp_entry<MT>, &rew_vjp_entry<MT>, &step_vjp_entry<MT>};
+                     &random_state, &observe, &vjp_entry<MT>, &rew_vjp_entry<MT>, &step_vjp_entry<MT>, &step_jac_entry<MT>};
   }
 };
 

@@ -25,6 +25,8 @@ SEM_AHEAD_ACCUMULATED_T = 2  # opt-in: diffrax's accumulated-time clock as the C
 # CoreEnvironment.sim_ahead_semantics -> excenv_semantics_t
 SEMANTICS = {"step": SEM_STEP, "ahead": SEM_AHEAD, "ahead_accumulated_t": SEM_AHEAD_ACCUMULATED_T}
 F32, F64 = 0, 1
+JAC_STATE, JAC_OBS = 0, 1  # excenv_jac_rows_t: the rows of excenv_step_jacobian
+JAC_ROWS = {"state": JAC_STATE, "obs": JAC_OBS}
 OPT_NO_FUSED_ACTIONS = 1  # EXCENV_OPT_NO_FUSED_ACTIONS
 OPT_KEEP_CONSTANT_COLUMNS = 2  # EXCENV_OPT_KEEP_CONSTANT_COLUMNS
 ABI_VERSION = 7
@@ -120,6 +122,11 @@ PROTOTYPES = {
     # grad_action, opts, stream
     "excenv_step_vjp": (_ci, [_ci, _ci, _ci, _i64, _vp, _vp, _cd, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "excenv_step_vjp_bytes": (_i64, [_ci, _ci, _i32, _ci, _ci, _ci]),
+    # env, solver, dtype, B, rows, substeps, props, n_control, dt, env_tau, state_in, state_out, state_row_stride, action, its three
+    # strides (row, component, environment), row_kind, jacobian, opts, stream
+    "excenv_step_jacobian": (_ci, [_ci, _ci, _ci, _i64, _i64, _i32, _vp, _i32, _cd, _cd, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _ci,
+                                   _vp, _vp, _vp]),
+    "excenv_step_jacobian_bytes": (_i64, [_ci, _ci, _ci]),
     "excenv_state_from_observation": (_ci, [_ci, _ci, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "excenv_update_ref": (_ci, [_ci, _ci, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
     "excenv_observe": (_ci, [_ci, _ci, _i64, _vp, _vp, _vp, _vp, _vp]),
@@ -468,6 +475,11 @@ def step_vjp_bytes(env_id: int, dtype: torch.dtype, n_control: int = 0, grad_obs
                    grad_reward: bool = False) -> int:
     """excenv_step_vjp_bytes: the algorithmic bytes per environment of one excenv_step_vjp launch with these cotangent groups."""
     return lib().excenv_step_vjp_bytes(env_id, dtype_id(dtype), n_control, int(grad_obs), int(grad_state), int(grad_reward))
+
+
+def step_jacobian_bytes(env_id: int, dtype: torch.dtype, rows: str = "state") -> int:
+    """excenv_step_jacobian_bytes: the algorithmic bytes per step instance of one excenv_step_jacobian launch."""
+    return lib().excenv_step_jacobian_bytes(env_id, dtype_id(dtype), JAC_ROWS[rows])
 
 
 def state_from_observation(env_id, dtype, B, props: Props, control_idx: Sequence[int], obs: torch.Tensor,

@@ -406,6 +406,35 @@ int excenv_step_vjp(int env, int solver, int dtype, int64_t B, const excenv_prop
                     void* const* grad_state_in, void* grad_action, const excenv_launch_opts_t* opts, void* stream);
 int64_t excenv_step_vjp_bytes(int env, int dtype, int32_t n_control, int has_grad_obs, int has_grad_state, int has_grad_reward);
 
+/* ---- linearisation of excenv_step (what jax.jacobian gives through the reference's vmap_step): the Jacobians of `rows` stored
+ * steps of B environments each from ONE launch of step_jac_kernel (additions, same ABI version: a binder probes for the symbols).
+ * A step instance is (row n, environment i); its lane reads the step's two states and its action once and writes the Jacobian row
+ * by row, each row the arithmetic of excenv_step_vjp for a one-hot cotangent:
+ *   state_in, state_out : S pointers each; step n of leaf j starts at state_in[j][n * state_row_stride + i] and ends at
+ *                         state_out[j][n * state_row_stride + i], the state the forward returned (read, not recomputed). A single
+ *                         step has rows == 1; a lane-major state trajectory [N+1][B] passes state_out[j] = state_in[j] + B,
+ *                         state_row_stride = B and rows = N.
+ *   action              : element (action row k, component q, environment i) at k * action_row_stride + q * action_comp_stride +
+ *                         i * action_env_stride elements. Step n reads action row n / substeps. Row-major [B][A]: (0, 1, A);
+ *                         lane-major [K][A][B]: (A * B, B, 1). No alignment beyond the element's.
+ *   dt, env_tau         : the solver's step (tau of excenv_step, obs_stepsize of excenv_sim_ahead) and the environment's tau
+ *   row_kind            : EXCENV_JAC_STATE: R = S rows, row r = d new_state[r] / d (state, action);
+ *                         EXCENV_JAC_OBS: R = O rows, row r = d obs[r] / d (state, action) at the saved new state. The n_control
+ *                         reference columns of an observation are constants and have no rows; n_control is only validated.
+ *   jacobian            : (out) lane-major [rows][R][S + A][B]: columns 0 .. S-1 the state leaves, S .. S+A-1 the action components
+ * Never allocates or synchronises. B == 0 or rows == 0 returns EXCENV_OK without a launch. excenv_last_launch() names the form:
+ * "step_jac_kernel (V=1, state rows)" or "step_jac_kernel (V=1, observation rows)" (opts->envs_per_lane other than 0 or 1:
+ * EXCENV_EINVAL). EXCENV_ENULL names a missing pointer. EXCENV_EUNSUPPORTED: the saturated PMSM (pmsm_lut), per-environment
+ * property arrays, PMSM with substeps != 1. Subgradient conventions as excenv_sim_ahead_vjp; static parameters, references and
+ * bounds are not differentiated.
+ * excenv_step_jacobian_bytes (host only): the algorithmic bytes per step instance, w (2S + A + R (S + A)); -1 for a bad argument. */
+typedef enum { EXCENV_JAC_STATE = 0, EXCENV_JAC_OBS = 1 } excenv_jac_rows_t;
+int excenv_step_jacobian(int env, int solver, int dtype, int64_t B, int64_t rows, int32_t substeps, const excenv_props_t* props,
+                         int32_t n_control, double dt, double env_tau, const void* const* state_in, const void* const* state_out,
+                         int64_t state_row_stride, const void* action, int64_t action_row_stride, int64_t action_comp_stride,
+                         int64_t action_env_stride, int row_kind, void* jacobian, const excenv_launch_opts_t* opts, void* stream);
+int64_t excenv_step_jacobian_bytes(int env, int dtype, int row_kind);
+
 /* ---- replaces CoreEnvironment.vmap_generate_state_from_observation (core_env.py:689-705; per env e.g.
  * pendulum_env.py:331-364, pmsm_env.py:921-970): obs [B][O + n_control] row-major -> denormalised physical state leaves
  * state_out[S][B] and, for each controlled field control_idx[j], its denormalised reference leaf reference_out[j][B]
