@@ -18,8 +18,9 @@ void set_error(const char* fmt, ...);
 // Set by launch_dyn when raising a kernel's dynamic-LDS limit failed (the launch is then skipped and
 // check_launch reports the stored message instead of a generic launch error). Per thread, like the error string.
 static thread_local bool g_attr_failed = false;
-// Which form of the trajectory kernel the last excenv_sim_ahead[_ws] call of this thread enqueued (excenv_last_launch(): tests
-// assert that the path they mean to check is the one that ran; like the error string it is per thread and purely informational).
+// Which kernel form the last launching call of this thread enqueued: excenv_sim_ahead[_ws], excenv_step and the reverse-mode calls
+// (excenv_last_launch(): tests assert that the path they mean to check is the one that ran; like the error string it is per thread
+// and purely informational).
 extern thread_local const char* g_last_launch;  // defined in excenv_api.hip
 
 struct StepCall {
@@ -349,6 +350,7 @@ template <class M, typename T> static int launch_step(const StepCall& sc) {
     });
     return true;
   });
+  g_last_launch = general ? "step_kernel (general)" : V == 1 ? "step_kernel (V=1)" : V == 2 ? "step_kernel (V=2)" : "step_kernel (V=4)";
   return check_launch("excenv_step");
 }
 

@@ -172,7 +172,8 @@ def _check(rc: int, what: str):
 
 
 def last_launch() -> str:
-    """excenv_last_launch(): which trajectory-kernel form the last sim_ahead call of this thread enqueued."""
+    """excenv_last_launch(): which kernel form the last launching call of this thread enqueued: "sim_ahead_kernel (...)" and its
+    siblings after a sim_ahead call, "step_kernel (V=1|V=2|V=4|general)" after a step, the reverse-mode kernels after theirs."""
     return lib().excenv_last_launch().decode("utf-8", "replace")
 
 

@@ -191,10 +191,13 @@ typedef struct {
 /* ---- introspection -------------------------------------------------------------------- */
 int excenv_abi_version(void);
 const char* excenv_last_error(void);
-/* Name of the trajectory-kernel form the last excenv_sim_ahead[_ws] call of this thread enqueued ("" before the first):
+/* Name of the kernel form the last launching call of this thread enqueued ("" before the first). excenv_sim_ahead[_ws]:
  * "sim_ahead_kernel (V=1|V=2|V=4)", "sim_ahead_kernel (general)", "sim_ahead_kernel (row-major actions fused)",
- * "sim_ahead_emr_kernel", "sim_ahead_em_kernel[ (general)]", "transposition workspace + sim_ahead_kernel". Informational
- * (tests assert that the path they mean to check is the one that ran). */
+ * "sim_ahead_emr_kernel", "sim_ahead_em_kernel[ (general)]", "transposition workspace + sim_ahead_kernel". excenv_step:
+ * "step_kernel (V=1|V=2|V=4)" (a forced opts->envs_per_lane that the batch size or a state pointer off a 16-byte boundary does
+ * not allow runs, and reports, a narrower form), "step_kernel (general)" (per-environment properties, control columns or gym
+ * outputs). The reverse-mode calls name theirs below. Informational (tests assert that the path they mean to check is the one
+ * that ran). */
 const char* excenv_last_launch(void);
 /* S = physical_state_dim, A = action_dim, O = observation width without control columns, P = #static params. */
 int excenv_env_dims(int env, int32_t* S, int32_t* A, int32_t* O, int32_t* P);

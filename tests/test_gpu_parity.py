@@ -196,7 +196,10 @@ def test_vmap_step_matches_oracle(env_name, solver, dtype):
 @pytest.mark.parametrize("solver", SOLVERS)
 @pytest.mark.parametrize("env_name", ENV_NAMES)
 def test_vmap_sim_ahead_matches_oracle(env_name, solver, dtype, semantics):
-    """Lane-major fast path (V envs per lane) on a batch divisible by 4, K = 64."""
+    """The lean lane-major kernel at ONE environment per lane (what the batch rule gives B = 2048), K = 64. The wider lanes of every
+    instantiation are held against this form and the oracle in tests/test_gpu_lean_forms.py."""
+    from exciting_environments_amd import _native
+
     B, K = 2048, 64
     env, props, keep, spec = make_env(env_name, B, dtype, solver)
     env.sim_ahead_semantics = semantics
@@ -206,6 +209,7 @@ def test_vmap_sim_ahead_matches_oracle(env_name, solver, dtype, semantics):
     a_dev = env.new_actions_buffer(K)
     a_dev.copy_(torch.as_tensor(acts, device=env.device))
     obs, states, last = env.vmap_sim_ahead(to_state(env, st), a_dev, env.tau, env.tau)
+    assert _native.last_launch() == "sim_ahead_kernel (V=1)", _native.last_launch()
     sem = oracle.SEM_STEP if semantics == "step" else oracle.SEM_AHEAD
     o_ref, s_ref, l_ref = oracle.sim_ahead(env_name, solver, st, acts, props, spec["tau"], semantics=sem)
     assert tuple(obs.shape) == o_ref.shape
@@ -427,6 +431,7 @@ def test_step_kernel_envs_per_lane_variants_are_bit_identical(env_name):
     for vec in (1, 2, 4):
         env.launch_opts = _native.launch_opts(envs_per_lane=vec)
         outs.append(env.vmap_step(to_state(env, st), act))
+        assert _native.last_launch() == f"step_kernel (V={vec})", _native.last_launch()
     for obs, new in outs[1:]:
         assert torch.equal(obs, outs[0][0])
         for n in env.STATE_FIELDS:

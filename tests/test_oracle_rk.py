@@ -58,14 +58,30 @@ def _msd_exact(x0, v0, u, d, k, m, T):
     return (expm(M * T) @ np.array([x0, v0, u]))[:2]
 
 
-@pytest.mark.parametrize("solver,order", [("euler", 1), ("rk4", 4), ("tsit5", 5)])
-def test_convergence_order_on_mass_spring_damper(solver, order):
-    params = {"d": 1.0, "k": 100.0, "m": 1.0}
+def _msd_params(which):
+    """the defaults d = m = 1, which cannot tell a product from a quotient, and helpers_vjp.skewed_spec's d, k, m"""
+    from helpers_vjp import skewed_spec
+
+    if which == "default":
+        return {"d": 1.0, "k": 100.0, "m": 1.0}
+    p = skewed_spec("mass_spring_damper")["params"]
+    assert len({p["d"], p["k"], p["m"], 1.0}) == 4
+    return {n: float(p[n]) for n in ("d", "k", "m")}
+
+
+def _with_skewed(rows):
+    """every row once on the default specification (under the id it always had) and once on the skewed one"""
+    return [pytest.param(*r, w, id="-".join(map(str, r)) + ("" if w == "default" else "-skewed")) for w in ("default", "skewed") for r in rows]
+
+
+@pytest.mark.parametrize("solver,order,which", _with_skewed([("euler", 1), ("rk4", 4), ("tsit5", 5)]))
+def test_convergence_order_on_mass_spring_damper(solver, order, which):
+    params = _msd_params(which)
     pn = {"deflection": (-10, 10), "velocity": (-10, 10)}
     an = {"force": (-20, 20)}
     props, keep = oracle.make_props("mass_spring_damper", params, pn, an, np.float64, 1)
     T, a = 0.5, 0.35
-    exact = _msd_exact(1.0, -2.0, oracle.denormalize(a, -20, 20), 1.0, 100.0, 1.0, T)
+    exact = _msd_exact(1.0, -2.0, oracle.denormalize(a, -20, 20), params["d"], params["k"], params["m"], T)
     errs = []
     ns = [50, 100, 200] if order > 1 else [2000, 4000, 8000]
     for n in ns:
@@ -74,7 +90,7 @@ def test_convergence_order_on_mass_spring_damper(solver, order):
         errs.append(np.hypot(last[0][0] - exact[0], last[1][0] - exact[1]))
     rates = [np.log2(errs[i] / errs[i + 1]) for i in range(2)]
     for r in rates:
-        assert order - 0.25 < r < order + 0.4, (solver, errs, rates)
+        assert order - 0.25 < r < order + 0.4, (solver, which, errs, rates)
 
 
 def test_c1_stage_sees_next_action_only_in_ahead_semantics():
@@ -122,16 +138,21 @@ def test_rk4_ahead_first_step_by_hand():
         assert np.allclose(got, want, rtol=1e-14, atol=0)
 
 
-@pytest.mark.parametrize("env,solver,tol", [("pendulum", "tsit5", 2e-10), ("pendulum", "rk4", 5e-8), ("acrobot", "tsit5", 5e-9),
-                                            ("cartpole", "tsit5", 5e-9)])
-def test_nonlinear_systems_against_independent_scipy_integration(env, solver, tol):
+@pytest.mark.parametrize("env,solver,tol,which", _with_skewed([("pendulum", "tsit5", 2e-10), ("pendulum", "rk4", 5e-8),
+                                                               ("acrobot", "tsit5", 5e-9), ("cartpole", "tsit5", 5e-9)]))
+def test_nonlinear_systems_against_independent_scipy_integration(env, solver, tol, which):
     """Constant action, 200 fixed steps: the oracle's RK trajectory vs scipy's DOP853 (rtol 1e-13) on the same vector
     field written independently here from the reference formulas (pendulum_env.py:144-150, acrobot_env.py:171-197,
-    cart_pole_env.py:159-180)."""
+    cart_pole_env.py:159-180). Once on the default specification and once on helpers_vjp.skewed_spec (every parameter off its
+    default — acrobot's m_1 = m_2, l_c1 = l_c2, I_1 = I_2, pendulum's m = 1, cart-pole's m_c = 1 hide an index mix-up — and an
+    asymmetric action range): its parameters and action range feed both the vector field here and the oracle. Measured on the
+    skewed specification: Tsit5 1.2e-15 (pendulum), 3.6e-15 (acrobot), 2.8e-14 (cart-pole); RK4 pendulum 5.0e-13 (default 1.5e-13),
+    so its truncation bound of 5e-8 does not move."""
     from scipy.integrate import solve_ivp
-    from conftest import load_golden
+    from helpers import spec_of
+    from helpers_vjp import skewed_spec
 
-    g = load_golden(env)
+    g = spec_of(env) if which == "default" else skewed_spec(env)
     p = g["params"]
     a_norm = 0.3
     (lo, hi), = g["act_norm"].values()
