@@ -78,14 +78,49 @@ static int check_common(const char* fn, int env, int solver, int dtype, int64_t 
   return EXCENV_OK;
 }
 
+static int check_n_control(const char* fn, int n_control) {
+  if (n_control < 0 || n_control > EXCENV_MAX_CONTROL) { set_error("%s: bad n_control %d", fn, n_control); return EXCENV_EINVAL; }
+  return EXCENV_OK;
+}
+// The controlled fields are state leaves of the model: field j alone (for callers that check more of field j before field j + 1), or all
+static int check_control_idx_at(const char* fn, int env, int j, int32_t idx) {
+  if (idx < 0 || idx >= table_public(env)->S) { set_error("%s: control_idx[%d] out of range", fn, j); return EXCENV_EINVAL; }
+  return EXCENV_OK;
+}
+static int check_control_idx(const char* fn, int env, int n_control, const int32_t* control_idx) {
+  for (int j = 0; j < n_control; ++j)
+    if (int rc = check_control_idx_at(fn, env, j, control_idx[j])) return rc;
+  return EXCENV_OK;
+}
+
 static int check_control(const char* fn, int env, const excenv_control_t*& c) {
   if (c && c->n_control == 0) c = nullptr;
   if (!c) return EXCENV_OK;
-  if (c->n_control < 0 || c->n_control > EXCENV_MAX_CONTROL) { set_error("%s: bad n_control %d", fn, c->n_control); return EXCENV_EINVAL; }
+  if (int rc = check_n_control(fn, c->n_control)) return rc;
   for (int j = 0; j < c->n_control; ++j) {
-    if (c->control_idx[j] < 0 || c->control_idx[j] >= table_public(env)->S) { set_error("%s: control_idx[%d] out of range", fn, j); return EXCENV_EINVAL; }
+    if (int rc = check_control_idx_at(fn, env, j, c->control_idx[j])) return rc;
     if (!c->reference[j]) { set_error("%s: reference[%d] is NULL", fn, j); return EXCENV_ENULL; }
   }
+  return EXCENV_OK;
+}
+
+// Is any property of the model a per-environment array?
+static bool props_per_env(const EnvVTable* t, const excenv_props_t* props) {
+  bool per_env = false;
+  for (int j = 0; j < t->P; ++j) per_env |= props->static_params[j].per_env != nullptr;
+  for (int j = 0; j < t->S; ++j) per_env |= props->state_min[j].per_env != nullptr || props->state_max[j].per_env != nullptr;
+  for (int j = 0; j < t->A; ++j) per_env |= props->action_min[j].per_env != nullptr || props->action_max[j].per_env != nullptr;
+  return per_env;
+}
+
+// What every reverse-mode call asks of its properties, in two parts because the calls check other arguments in between
+static int check_reverse_props(const char* fn, const excenv_props_t* props) {
+  if (!props) { set_error("%s: props is NULL", fn); return EXCENV_ENULL; }
+  if (props->pmsm_lut) { set_error("%s: the saturated PMSM (pmsm_lut) has no reverse mode", fn); return EXCENV_EUNSUPPORTED; }
+  return EXCENV_OK;
+}
+static int check_broadcast_props(const char* fn, int env, const excenv_props_t* props) {
+  if (props_per_env(table_public(env), props)) { set_error("%s: per-environment property arrays are not supported (broadcast properties only)", fn); return EXCENV_EUNSUPPORTED; }
   return EXCENV_OK;
 }
 
@@ -178,9 +213,7 @@ static SimFacts sim_facts(int env, const EnvVTable* t, int solver, int dtype, in
   SimFacts f{};
   f.env = env; f.S = t->S; f.A = t->A; f.O = t->O; f.elem = dtype == EXCENV_F64 ? 8 : 4; f.solver = solver; f.semantics = semantics;
   f.B = B; f.K = K; f.substeps = substeps; f.action_layout = action_layout; f.traj_layout = traj_layout;
-  for (int j = 0; j < t->P; ++j) f.per_env_props |= props->static_params[j].per_env != nullptr;
-  for (int j = 0; j < t->S; ++j) f.per_env_props |= props->state_min[j].per_env != nullptr || props->state_max[j].per_env != nullptr;
-  for (int j = 0; j < t->A; ++j) f.per_env_props |= props->action_min[j].per_env != nullptr || props->action_max[j].per_env != nullptr;
+  f.per_env_props = props_per_env(t, props);
   f.lut = props->pmsm_lut != nullptr; f.n_control = n_control; f.refs_given = true;
   f.al_actions = f.al_obs = f.al_state_io = f.al_straj = f.al_reward = f.al_terminated = f.al_truncated = f.al_refs = 128;
   f.envs_per_lane = opts->envs_per_lane; f.env_major_mode = opts->env_major_mode; f.flags = opts->flags;
@@ -329,7 +362,7 @@ static int sim_ahead_vjp_call(const char* fn, bool pgrad, int env, int solver, i
   if (action_layout == EXCENV_LAYOUT_TILED) { set_error("%s: the tiled layout has no reverse mode (lane-major or env-major actions)", fn); return EXCENV_EUNSUPPORTED; }
   if (action_layout != EXCENV_LAYOUT_ENV_MAJOR && action_layout != EXCENV_LAYOUT_LANE_MAJOR) { set_error("%s: bad layout id", fn); return EXCENV_EINVAL; }
   if (!props || !state_traj || !grad_state_in || ((!actions || !grad_actions) && K > 0)) { set_error("%s: NULL argument", fn); return EXCENV_ENULL; }
-  if (props->pmsm_lut) { set_error("%s: the saturated PMSM (pmsm_lut) has no reverse mode", fn); return EXCENV_EUNSUPPORTED; }
+  if (int rc = check_reverse_props(fn, props)) return rc;
   const EnvVTable* t = table_public(env);
   bool params_aligned = true;
   if (pgrad) {
@@ -345,15 +378,9 @@ static int sim_ahead_vjp_call(const char* fn, bool pgrad, int env, int solver, i
     if (!any) { set_error("%s: every entry of grad_params is NULL (excenv_sim_ahead_vjp is the call without parameter gradients)", fn); return EXCENV_EINVAL; }
   }
   const int nc = control ? control->n_control : 0;
-  if (nc < 0 || nc > EXCENV_MAX_CONTROL) { set_error("%s: bad n_control %d", fn, nc); return EXCENV_EINVAL; }
+  if (int rc = check_n_control(fn, nc)) return rc;
   if (int rc = check_opts(fn, opts)) return rc;
-  {
-    bool per_env = false;
-    for (int j = 0; j < t->P; ++j) per_env |= props->static_params[j].per_env != nullptr;
-    for (int j = 0; j < t->S; ++j) per_env |= props->state_min[j].per_env != nullptr || props->state_max[j].per_env != nullptr;
-    for (int j = 0; j < t->A; ++j) per_env |= props->action_min[j].per_env != nullptr || props->action_max[j].per_env != nullptr;
-    if (per_env) { set_error("%s: per-environment property arrays are not supported (broadcast properties only)", fn); return EXCENV_EUNSUPPORTED; }
-  }
+  if (int rc = check_broadcast_props(fn, env, props)) return rc;
   const int elem = dtype == EXCENV_F64 ? 8 : 4;
   const void* k_actions = actions;
   const bool transposed = action_layout == EXCENV_LAYOUT_ENV_MAJOR && B > 0 && K > 0;
@@ -471,10 +498,9 @@ int excenv_rew_trunc_term(int env, int dtype, int64_t B, int64_t rows, const exc
 int excenv_rew_reads(int env, int32_t n_control, const int32_t* control_idx, uint8_t reads[EXCENV_MAX_STATE]) {
   const EnvVTable* t = table_public(env);
   if (!t) { set_error("excenv_rew_reads: bad env id %d", env); return EXCENV_EINVAL; }
-  if (n_control < 0 || n_control > EXCENV_MAX_CONTROL) { set_error("excenv_rew_reads: bad n_control %d", n_control); return EXCENV_EINVAL; }
+  if (int rc = check_n_control("excenv_rew_reads", n_control)) return rc;
   if (!reads || (n_control > 0 && !control_idx)) { set_error("excenv_rew_reads: NULL argument"); return EXCENV_ENULL; }
-  for (int j = 0; j < n_control; ++j)
-    if (control_idx[j] < 0 || control_idx[j] >= t->S) { set_error("excenv_rew_reads: control_idx[%d] out of range", j); return EXCENV_EINVAL; }
+  if (int rc = check_control_idx("excenv_rew_reads", env, n_control, control_idx)) return rc;
   uint8_t r[EXCENV_MAX_STATE];
   reward_reads(env, n_control, control_idx, r);
   std::copy(r, r + EXCENV_MAX_STATE, reads);
@@ -514,9 +540,7 @@ int excenv_rew_vjp(int env, int dtype, int64_t B, int64_t rows, const excenv_pro
     const int64_t sb = ref_strides ? ref_strides[2 * j] : 1, sk = ref_strides ? ref_strides[2 * j + 1] : 0;
     fast_ok = fast_ok && sb == 1 && (sk == 0 || sk == B) && align_of(control->reference[j]) >= 16;
   }
-  for (int j = 0; j < t->P; ++j) fast_ok = fast_ok && !props->static_params[j].per_env;
-  for (int j = 0; j < t->S; ++j) fast_ok = fast_ok && !props->state_min[j].per_env && !props->state_max[j].per_env;
-  for (int j = 0; j < t->A; ++j) fast_ok = fast_ok && !props->action_min[j].per_env && !props->action_max[j].per_env;
+  fast_ok = fast_ok && !props_per_env(t, props);
   const int V = rew_vjp_envs_per_lane(elem, opts->envs_per_lane, fast_ok);
   if (V == 0) {
     set_error("%s: opts.envs_per_lane = %d is not available (1, or %d with lane-major 16-byte aligned arrays, batch_size %% %d == 0 and "
@@ -549,30 +573,23 @@ int excenv_step_vjp(int env, int solver, int dtype, int64_t B, const excenv_prop
                     void* const* grad_state_in, void* grad_action, const excenv_launch_opts_t* opts, void* stream) {
   const char* fn = "excenv_step_vjp";
   if (int rc = check_common(fn, env, solver, dtype, B)) return rc;
-  if (!props) { set_error("%s: props is NULL", fn); return EXCENV_ENULL; }
-  if (props->pmsm_lut) { set_error("%s: the saturated PMSM (pmsm_lut) has no reverse mode", fn); return EXCENV_EUNSUPPORTED; }
+  if (int rc = check_reverse_props(fn, props)) return rc;
   const EnvVTable* t = table_public(env);
   if (control && control->n_control == 0) control = nullptr;
   const int nc = control ? control->n_control : 0;
-  if (nc < 0 || nc > EXCENV_MAX_CONTROL) { set_error("%s: bad n_control %d", fn, nc); return EXCENV_EINVAL; }
+  if (int rc = check_n_control(fn, nc)) return rc;
   if (grad_reward) {  // the reward reads the controlled fields and their references; without any it is a constant
     if (!control) {
       set_error("%s: grad_reward without control references (the reward depends on the state through the controlled fields only)", fn);
       return EXCENV_EUNSUPPORTED;
     }
     for (int j = 0; j < nc; ++j) {
-      if (control->control_idx[j] < 0 || control->control_idx[j] >= t->S) { set_error("%s: control_idx[%d] out of range", fn, j); return EXCENV_EINVAL; }
+      if (int rc = check_control_idx_at(fn, env, j, control->control_idx[j])) return rc;
       if (!control->reference[j]) { set_error("%s: reference[%d] is NULL (grad_reward reads the references)", fn, j); return EXCENV_ENULL; }
     }
   }
   if (int rc = check_opts(fn, opts)) return rc;
-  {
-    bool per_env = false;
-    for (int j = 0; j < t->P; ++j) per_env |= props->static_params[j].per_env != nullptr;
-    for (int j = 0; j < t->S; ++j) per_env |= props->state_min[j].per_env != nullptr || props->state_max[j].per_env != nullptr;
-    for (int j = 0; j < t->A; ++j) per_env |= props->action_min[j].per_env != nullptr || props->action_max[j].per_env != nullptr;
-    if (per_env) { set_error("%s: per-environment property arrays are not supported (broadcast properties only)", fn); return EXCENV_EUNSUPPORTED; }
-  }
+  if (int rc = check_broadcast_props(fn, env, props)) return rc;
   if (B == 0) return EXCENV_OK;  // nothing to write: no launch, whatever the (empty) arrays' addresses are
   if (!state_in) { set_error("%s: state_in is NULL", fn); return EXCENV_ENULL; }
   if (!action) { set_error("%s: action is NULL", fn); return EXCENV_ENULL; }
@@ -612,19 +629,12 @@ int excenv_step_jacobian(int env, int solver, int dtype, int64_t B, int64_t rows
   if (int rc = check_common(fn, env, solver, dtype, B)) return rc;
   if (rows < 0) { set_error("%s: bad rows %lld", fn, (long long)rows); return EXCENV_EINVAL; }
   if (substeps < 1) { set_error("%s: bad substeps %d (at least 1)", fn, (int)substeps); return EXCENV_EINVAL; }
-  if (n_control < 0 || n_control > EXCENV_MAX_CONTROL) { set_error("%s: bad n_control %d", fn, (int)n_control); return EXCENV_EINVAL; }
+  if (int rc = check_n_control(fn, n_control)) return rc;
   if (row_kind != EXCENV_JAC_STATE && row_kind != EXCENV_JAC_OBS) { set_error("%s: bad row_kind %d", fn, row_kind); return EXCENV_EINVAL; }
-  if (!props) { set_error("%s: props is NULL", fn); return EXCENV_ENULL; }
-  if (props->pmsm_lut) { set_error("%s: the saturated PMSM (pmsm_lut) has no reverse mode", fn); return EXCENV_EUNSUPPORTED; }
+  if (int rc = check_reverse_props(fn, props)) return rc;
   const EnvVTable* t = table_public(env);
   if (int rc = check_opts(fn, opts)) return rc;
-  {
-    bool per_env = false;
-    for (int j = 0; j < t->P; ++j) per_env |= props->static_params[j].per_env != nullptr;
-    for (int j = 0; j < t->S; ++j) per_env |= props->state_min[j].per_env != nullptr || props->state_max[j].per_env != nullptr;
-    for (int j = 0; j < t->A; ++j) per_env |= props->action_min[j].per_env != nullptr || props->action_max[j].per_env != nullptr;
-    if (per_env) { set_error("%s: per-environment property arrays are not supported (broadcast properties only)", fn); return EXCENV_EUNSUPPORTED; }
-  }
+  if (int rc = check_broadcast_props(fn, env, props)) return rc;
   const int V = step_jac_envs_per_lane(opts->envs_per_lane);
   if (V == 0) {
     set_error("%s: opts.envs_per_lane = %d is not available (this kernel has the one-instance-per-lane form only)", fn, opts->envs_per_lane);
@@ -652,10 +662,9 @@ int excenv_state_from_observation(int env, int dtype, int64_t B, const excenv_pr
                                   const int32_t* control_idx, const void* obs, void* const* state_out,
                                   void* const* reference_out, void* stream) {
   if (int rc = check_common("excenv_state_from_observation", env, 0, dtype, B)) return rc;
-  if (n_control < 0 || n_control > EXCENV_MAX_CONTROL) { set_error("excenv_state_from_observation: bad n_control %d", n_control); return EXCENV_EINVAL; }
+  if (int rc = check_n_control("excenv_state_from_observation", n_control)) return rc;
   if (!props || !obs || !state_out || (n_control > 0 && (!control_idx || !reference_out))) { set_error("excenv_state_from_observation: NULL argument"); return EXCENV_ENULL; }
-  for (int j = 0; j < n_control; ++j)
-    if (control_idx[j] < 0 || control_idx[j] >= table_public(env)->S) { set_error("excenv_state_from_observation: control_idx[%d] out of range", j); return EXCENV_EINVAL; }
+  if (int rc = check_control_idx("excenv_state_from_observation", env, n_control, control_idx)) return rc;
   int trc;
   const EnvVTable* t = table_for(env, props, &trc);
   if (!t) return trc;
@@ -668,9 +677,8 @@ int excenv_observe(int env, int dtype, int64_t B, const excenv_props_t* props, c
   if (int rc = check_common("excenv_observe", env, 0, dtype, B)) return rc;
   if (!props || !state || !obs) { set_error("excenv_observe: NULL argument"); return EXCENV_ENULL; }
   if (control) {
-    if (control->n_control < 0 || control->n_control > EXCENV_MAX_CONTROL) { set_error("excenv_observe: bad n_control %d", control->n_control); return EXCENV_EINVAL; }
-    for (int j = 0; j < control->n_control; ++j)
-      if (control->control_idx[j] < 0 || control->control_idx[j] >= table_public(env)->S) { set_error("excenv_observe: control_idx[%d] out of range", j); return EXCENV_EINVAL; }
+    if (int rc = check_n_control("excenv_observe", control->n_control)) return rc;
+    if (int rc = check_control_idx("excenv_observe", env, control->n_control, control->control_idx)) return rc;
   }
   int trc;
   const EnvVTable* t = table_for(env, props, &trc);
@@ -683,10 +691,9 @@ int excenv_update_ref(int env, int dtype, int64_t B, const excenv_props_t* props
                       const int32_t* control_idx, void* const* reference, int64_t* keys, int64_t* hold,
                       int32_t hold_steps_min, int32_t hold_steps_max, void* stream) {
   if (int rc = check_common("excenv_update_ref", env, 0, dtype, B)) return rc;
-  if (n_control < 0 || n_control > EXCENV_MAX_CONTROL) { set_error("excenv_update_ref: bad n_control %d", n_control); return EXCENV_EINVAL; }
+  if (int rc = check_n_control("excenv_update_ref", n_control)) return rc;
   if (!props || !keys || !hold || (n_control > 0 && (!control_idx || !reference))) { set_error("excenv_update_ref: NULL argument"); return EXCENV_ENULL; }
-  for (int j = 0; j < n_control; ++j)
-    if (control_idx[j] < 0 || control_idx[j] >= table_public(env)->S) { set_error("excenv_update_ref: control_idx[%d] out of range", j); return EXCENV_EINVAL; }
+  if (int rc = check_control_idx("excenv_update_ref", env, n_control, control_idx)) return rc;
   int trc;
   const EnvVTable* t = table_for(env, props, &trc);
   if (!t) return trc;
@@ -699,14 +706,14 @@ int excenv_update_ref_to(int env, int dtype, int64_t B, const excenv_props_t* pr
                          const int64_t* hold_in, void* const* reference_out, int64_t* keys_out, int64_t* hold_out,
                          int32_t hold_steps_min, int32_t hold_steps_max, void* stream) {
   if (int rc = check_common("excenv_update_ref_to", env, 0, dtype, B)) return rc;
-  if (n_control < 0 || n_control > EXCENV_MAX_CONTROL) { set_error("excenv_update_ref_to: bad n_control %d", n_control); return EXCENV_EINVAL; }
+  if (int rc = check_n_control("excenv_update_ref_to", n_control)) return rc;
   if (!props || !keys_in || !hold_in || !keys_out || !hold_out || (n_control > 0 && (!control_idx || !reference_in || !reference_out))) {
     set_error("excenv_update_ref_to: NULL argument");
     return EXCENV_ENULL;
   }
   if (keys_in == keys_out || hold_in == hold_out) { set_error("excenv_update_ref_to: outputs must not alias the inputs (use excenv_update_ref)"); return EXCENV_EINVAL; }
   for (int j = 0; j < n_control; ++j) {
-    if (control_idx[j] < 0 || control_idx[j] >= table_public(env)->S) { set_error("excenv_update_ref_to: control_idx[%d] out of range", j); return EXCENV_EINVAL; }
+    if (int rc = check_control_idx_at("excenv_update_ref_to", env, j, control_idx[j])) return rc;
     if (reference_in[j] == reference_out[j]) { set_error("excenv_update_ref_to: outputs must not alias the inputs (use excenv_update_ref)"); return EXCENV_EINVAL; }
   }
   int trc;

@@ -110,4 +110,11 @@ template <class M, typename T> static int launch_rew_vjp(const RewVjpCall& rc) {
   return check_launch("excenv_rew_vjp");
 }
 
+// EnvVTable::rew_vjp (launch.hpp), instantiated in rew_vjp.hip. The reward does not read the saturated model's tables: its entry is
+// the linear PMSM's.
+template <template <typename> class MT> int rew_vjp_entry(const RewVjpCall& rc) {
+  if constexpr (MT<float>::HAS_LUT) return rew_vjp_entry<Pmsm>(rc);
+  else return EXCENV_BY_DTYPE(launch_rew_vjp, MT, rc);
+}
+
 }  // namespace excenv

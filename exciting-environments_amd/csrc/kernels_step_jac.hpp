@@ -93,16 +93,8 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(2)))
 template <class M, typename T> static int launch_step_jac(const StepJacCall& jc) {
   StepJacArgs<T, M> ka;
   std::memset(&ka, 0, sizeof(ka));
-  if (fill_props<T, M>(ka.kp, jc.props)) {
-    set_error("excenv_step_jacobian: per-environment property arrays are not supported");
-    return EXCENV_EUNSUPPORTED;
-  }
-  double coef;
-  if (int rc = pmsm_coef<M>(jc.props, jc.env_tau, &coef, false)) return rc;
-  if (M::IS_PMSM && jc.substeps != 1) {
-    set_error("PMSM: obs_stepsize must equal action_stepsize (reference pmsm_env.py:787)");
-    return EXCENV_EUNSUPPORTED;
-  }
+  if (int rc = reverse_preamble("excenv_step_jacobian", ka, jc.props, jc.dt, jc.env_tau, false)) return rc;
+  if (int rc = pmsm_one_substep<M>(jc.substeps)) return rc;
   ka.B = jc.B;
   ka.rows = jc.rows;
   ka.substeps = jc.substeps;
@@ -117,9 +109,6 @@ template <class M, typename T> static int launch_step_jac(const StepJacCall& jc)
   ka.a_comp = jc.a_comp;
   ka.a_env = jc.a_env;
   ka.jac = (T*)jc.jacobian;
-  ka.dt = (T)jc.dt;
-  ka.env_tau = (T)jc.env_tau;
-  ka.adv_coef = (T)coef;
   if (jc.B == 0 || jc.rows == 0) return EXCENV_OK;
   const int64_t per_row = (jc.B + BLOCK - 1) / BLOCK;
   if (per_row * jc.rows > (int64_t)0x7fffffff) {
@@ -141,9 +130,14 @@ template <class M, typename T> static int launch_step_jac(const StepJacCall& jc)
   return check_launch("excenv_step_jacobian");
 }
 
-// What a model's translation unit (step_jac_<model>.hip) defines as its specialisation of step_jac_entry (launch.hpp: EnvVTable::step_jac)
-template <template <typename> class MT> static int launch_step_jac_any(const StepJacCall& jc) {
-  return jc.dtype == EXCENV_F32 ? launch_step_jac<MT<float>, float>(jc) : launch_step_jac<MT<double>, double>(jc);
+// EnvVTable::step_jac (launch.hpp): a model's translation unit step_jac_<model>.hip instantiates it
+template <template <typename> class MT> int step_jac_entry(const StepJacCall& jc) {
+  if constexpr (MT<float>::HAS_LUT) {
+    set_error("excenv_step_jacobian: the saturated PMSM (pmsm_lut) has no reverse mode");
+    return EXCENV_EUNSUPPORTED;
+  } else {
+    return EXCENV_BY_DTYPE(launch_step_jac, MT, jc);
+  }
 }
 
 }  // namespace excenv

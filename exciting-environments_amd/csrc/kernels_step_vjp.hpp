@@ -93,12 +93,7 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(2)))
 template <class M, typename T> static int launch_step_vjp(const StepVjpCall& sc) {
   StepVjpArgs<T, M> ka;
   std::memset(&ka, 0, sizeof(ka));
-  if (fill_props<T, M>(ka.kp, sc.props)) {
-    set_error("excenv_step_vjp: per-environment property arrays are not supported");
-    return EXCENV_EUNSUPPORTED;
-  }
-  double coef;
-  if (int rc = pmsm_coef<M>(sc.props, sc.tau, &coef, false)) return rc;
+  if (int rc = reverse_preamble("excenv_step_vjp", ka, sc.props, sc.tau, sc.tau, false)) return rc;
   ka.B = sc.B;
   ka.n_control = sc.control ? sc.control->n_control : 0;
   for (int j = 0; j < ka.n_control; ++j) {
@@ -115,9 +110,6 @@ template <class M, typename T> static int launch_step_vjp(const StepVjpCall& sc)
   ka.g_obs = (const T*)sc.grad_obs;
   ka.g_reward = (const T*)sc.grad_reward;
   ka.g_action = (T*)sc.grad_action;
-  ka.dt = (T)sc.tau;
-  ka.env_tau = (T)sc.tau;
-  ka.adv_coef = (T)coef;
   if (sc.B == 0) return EXCENV_OK;
   const dim3 grid((unsigned)((sc.B + BLOCK - 1) / BLOCK)), block(BLOCK);
   const hipStream_t stream = (hipStream_t)sc.stream;
@@ -133,9 +125,14 @@ template <class M, typename T> static int launch_step_vjp(const StepVjpCall& sc)
   return check_launch("excenv_step_vjp");
 }
 
-// What a model's translation unit (step_vjp_<model>.hip) defines as its specialisation of step_vjp_entry (launch.hpp: EnvVTable::step_vjp)
-template <template <typename> class MT> static int launch_step_vjp_any(const StepVjpCall& sc) {
-  return sc.dtype == EXCENV_F32 ? launch_step_vjp<MT<float>, float>(sc) : launch_step_vjp<MT<double>, double>(sc);
+// EnvVTable::step_vjp (launch.hpp): a model's translation unit step_vjp_<model>.hip instantiates it
+template <template <typename> class MT> int step_vjp_entry(const StepVjpCall& sc) {
+  if constexpr (MT<float>::HAS_LUT) {
+    set_error("excenv_step_vjp: the saturated PMSM (pmsm_lut) has no reverse mode");
+    return EXCENV_EUNSUPPORTED;
+  } else {
+    return EXCENV_BY_DTYPE(launch_step_vjp, MT, sc);
+  }
 }
 
 }  // namespace excenv

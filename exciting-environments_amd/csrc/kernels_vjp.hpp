@@ -620,17 +620,9 @@ __global__ void __launch_bounds__(BLOCK) vjp_raw_rows_kernel(const VjpArgs<T, M>
 template <class M, typename T> static int launch_vjp(const VjpCall& vc) {
   VjpParamArgs<T, M> ka;  // the plain launch passes its VjpArgs part
   std::memset(&ka, 0, sizeof(ka));
-  if (fill_props<T, M>(ka.kp, vc.props)) {
-    set_error("excenv_sim_ahead_vjp: per-environment property arrays are not supported");
-    return EXCENV_EUNSUPPORTED;
-  }
   const bool ahead = vc.semantics == EXCENV_SEM_AHEAD;
-  double coef;
-  if (int rc = pmsm_coef<M>(vc.props, vc.env_tau, &coef, ahead)) return rc;
-  if (M::IS_PMSM && vc.substeps != 1) {
-    set_error("PMSM: obs_stepsize must equal action_stepsize (reference pmsm_env.py:787)");
-    return EXCENV_EUNSUPPORTED;
-  }
+  if (int rc = reverse_preamble("excenv_sim_ahead_vjp", ka, vc.props, vc.obs_stepsize, vc.env_tau, ahead)) return rc;
+  if (int rc = pmsm_one_substep<M>(vc.substeps)) return rc;
   ka.B = vc.B;
   ka.K = vc.K;
   ka.substeps = vc.substeps;
@@ -645,9 +637,6 @@ template <class M, typename T> static int launch_vjp(const VjpCall& vc) {
     ka.g_last[j] = vc.grad_last_state ? (const T*)vc.grad_last_state[j] : nullptr;
     ka.g_state_in[j] = (T*)vc.grad_state_in[j];
   }
-  ka.dt = (T)vc.obs_stepsize;
-  ka.env_tau = (T)vc.env_tau;
-  ka.adv_coef = (T)coef;
   ka.lin_stop = (T)(vc.env_tau * (double)(vc.K > 0 ? vc.K - 1 : 0));
   const bool pgrad = vc.grad_params != nullptr;
   for (int j = 0; pgrad && j < M::P; ++j) ka.g_params[j] = (T*)vc.grad_params[j];
@@ -688,9 +677,14 @@ template <class M, typename T> static int launch_vjp(const VjpCall& vc) {
   return check_launch("excenv_sim_ahead_vjp");
 }
 
-// What a model's translation unit (vjp_<model>.hip) defines as its specialisation of vjp_entry (launch.hpp: EnvVTable::sim_vjp)
-template <template <typename> class MT> static int launch_vjp_any(const VjpCall& vc) {
-  return vc.dtype == EXCENV_F32 ? launch_vjp<MT<float>, float>(vc) : launch_vjp<MT<double>, double>(vc);
+// EnvVTable::sim_vjp (launch.hpp): a model's translation unit vjp_<model>.hip instantiates it
+template <template <typename> class MT> int vjp_entry(const VjpCall& vc) {
+  if constexpr (MT<float>::HAS_LUT) {
+    set_error("excenv_sim_ahead_vjp: the saturated PMSM (pmsm_lut) has no reverse mode");
+    return EXCENV_EUNSUPPORTED;
+  } else {
+    return EXCENV_BY_DTYPE(launch_vjp, MT, vc);
+  }
 }
 
 }  // namespace excenv

@@ -141,47 +141,17 @@ struct EnvVTable {
   int (*step_jac)(const StepJacCall&);  // Jacobians of step, row by row (kernels_step_jac.hpp)
 };
 
-// The reverse-mode launcher of a model: declared here so that it sits in the same table as every other entry point, defined in the
-// model's own translation unit vjp_<model>.hip (the saturated PMSM's reports that it has none)
+// The reverse-mode entries of a model: declared here so that they sit in the same table as every other entry point, each defined
+// next to its launcher (kernels_vjp.hpp, kernels_rew_vjp.hpp, kernels_step_vjp.hpp, kernels_step_jac.hpp) and instantiated in the
+// translation units that hold its kernels: vjp_<model>.hip, rew_vjp.hip, step_vjp_<model>.hip, step_jac_<model>.hip
 template <template <typename> class MT> int vjp_entry(const VjpCall&);
-template <> int vjp_entry<Pendulum>(const VjpCall&);
-template <> int vjp_entry<MassSpringDamper>(const VjpCall&);
-template <> int vjp_entry<CartPole>(const VjpCall&);
-template <> int vjp_entry<Acrobot>(const VjpCall&);
-template <> int vjp_entry<FluidTank>(const VjpCall&);
-template <> int vjp_entry<Pmsm>(const VjpCall&);
-template <> int vjp_entry<PmsmSat>(const VjpCall&);
-// The transposed reward's launcher, likewise: all seven defined in rew_vjp.hip (the saturated PMSM's is the linear model's)
 template <template <typename> class MT> int rew_vjp_entry(const RewVjpCall&);
-template <> int rew_vjp_entry<Pendulum>(const RewVjpCall&);
-template <> int rew_vjp_entry<MassSpringDamper>(const RewVjpCall&);
-template <> int rew_vjp_entry<CartPole>(const RewVjpCall&);
-template <> int rew_vjp_entry<Acrobot>(const RewVjpCall&);
-template <> int rew_vjp_entry<FluidTank>(const RewVjpCall&);
-template <> int rew_vjp_entry<Pmsm>(const RewVjpCall&);
-template <> int rew_vjp_entry<PmsmSat>(const RewVjpCall&);
-
-// The reverse-mode step launcher, likewise: defined in the model's own translation unit step_vjp_<model>.hip (the saturated
-// PMSM's reports that it has none)
 template <template <typename> class MT> int step_vjp_entry(const StepVjpCall&);
-template <> int step_vjp_entry<Pendulum>(const StepVjpCall&);
-template <> int step_vjp_entry<MassSpringDamper>(const StepVjpCall&);
-template <> int step_vjp_entry<CartPole>(const StepVjpCall&);
-template <> int step_vjp_entry<Acrobot>(const StepVjpCall&);
-template <> int step_vjp_entry<FluidTank>(const StepVjpCall&);
-template <> int step_vjp_entry<Pmsm>(const StepVjpCall&);
-template <> int step_vjp_entry<PmsmSat>(const StepVjpCall&);
-
-// The step Jacobian launcher, likewise: defined in the model's own translation unit step_jac_<model>.hip (the saturated PMSM's
-// reports that it has none)
 template <template <typename> class MT> int step_jac_entry(const StepJacCall&);
-template <> int step_jac_entry<Pendulum>(const StepJacCall&);
-template <> int step_jac_entry<MassSpringDamper>(const StepJacCall&);
-template <> int step_jac_entry<CartPole>(const StepJacCall&);
-template <> int step_jac_entry<Acrobot>(const StepJacCall&);
-template <> int step_jac_entry<FluidTank>(const StepJacCall&);
-template <> int step_jac_entry<Pmsm>(const StepJacCall&);
-template <> int step_jac_entry<PmsmSat>(const StepJacCall&);
+
+// The one choice of the element type: launcher<MT<float>, float>(call) or launcher<MT<double>, double>(call) by the call's dtype
+#define EXCENV_BY_DTYPE(launcher, MT, call) \
+  ((call).dtype == EXCENV_F32 ? launcher<MT<float>, float>(call) : launcher<MT<double>, double>(call))
 
 template <typename T, class M>
 static bool fill_props(KProps<T, M>& kp, const excenv_props_t* p) {
@@ -288,6 +258,31 @@ template <class M> static int pmsm_coef(const excenv_props_t* p, double env_tau,
     }
     *coef = (d.value + 0.5) * env_tau;
   }
+  return EXCENV_OK;
+}
+
+// The trajectory calls of the PMSM take one step per action row
+template <class M> static int pmsm_one_substep(int32_t substeps) {
+  if (M::IS_PMSM && substeps != 1) {
+    set_error("PMSM: obs_stepsize must equal action_stepsize (reference pmsm_env.py:787)");
+    return EXCENV_EUNSUPPORTED;
+  }
+  return EXCENV_OK;
+}
+
+// What the reverse launchers start from: broadcast properties (anything else is refused under the entry point's name `fn`), the
+// dead-time coefficient and the step sizes in the element type. Args: VjpParamArgs, StepVjpArgs or StepJacArgs.
+template <typename T, class M, template <typename, class> class Args>
+static int reverse_preamble(const char* fn, Args<T, M>& ka, const excenv_props_t* props, double dt, double env_tau, bool ahead) {
+  if (fill_props<T, M>(ka.kp, props)) {
+    set_error("%s: per-environment property arrays are not supported", fn);
+    return EXCENV_EUNSUPPORTED;
+  }
+  double coef;
+  if (int rc = pmsm_coef<M>(props, env_tau, &coef, ahead)) return rc;
+  ka.dt = (T)dt;
+  ka.env_tau = (T)env_tau;
+  ka.adv_coef = (T)coef;
   return EXCENV_OK;
 }
 
@@ -432,10 +427,7 @@ template <class M, typename T> static int launch_sim(const SimCall& sc) {
   fill_props<T, M>(ka.kp, sc.props);
   double coef;
   if (int rc = pmsm_coef<M>(sc.props, sc.env_tau, &coef, sc.semantics != EXCENV_SEM_STEP)) return rc;
-  if (M::IS_PMSM && sc.substeps != 1) {
-    set_error("PMSM: obs_stepsize must equal action_stepsize (reference pmsm_env.py:787)");
-    return EXCENV_EUNSUPPORTED;
-  }
+  if (int rc = pmsm_one_substep<M>(sc.substeps)) return rc;
   ka.B = sc.B;
   ka.K = sc.K;
   ka.substeps = sc.substeps;
@@ -700,27 +692,13 @@ template <class M, typename T> static int launch_random_state(const RandomStateC
 }
 
 template <template <typename> class MT> struct EnvEntry {
-  static int step(const StepCall& sc) {
-    return sc.dtype == EXCENV_F32 ? launch_step<MT<float>, float>(sc) : launch_step<MT<double>, double>(sc);
-  }
-  static int sim(const SimCall& sc) {
-    return sc.dtype == EXCENV_F32 ? launch_sim<MT<float>, float>(sc) : launch_sim<MT<double>, double>(sc);
-  }
-  static int traj_gym(const TrajGymCall& gc) {
-    return gc.dtype == EXCENV_F32 ? launch_traj_gym<MT<float>, float>(gc) : launch_traj_gym<MT<double>, double>(gc);
-  }
-  static int from_obs(const FromObsCall& fc) {
-    return fc.dtype == EXCENV_F32 ? launch_from_obs<MT<float>, float>(fc) : launch_from_obs<MT<double>, double>(fc);
-  }
-  static int update_ref(const RefGenCall& rc) {
-    return rc.dtype == EXCENV_F32 ? launch_update_ref<MT<float>, float>(rc) : launch_update_ref<MT<double>, double>(rc);
-  }
-  static int random_state(const RandomStateCall& rc) {
-    return rc.dtype == EXCENV_F32 ? launch_random_state<MT<float>, float>(rc) : launch_random_state<MT<double>, double>(rc);
-  }
-  static int observe(const ObserveCall& oc) {
-    return oc.dtype == EXCENV_F32 ? launch_observe<MT<float>, float>(oc) : launch_observe<MT<double>, double>(oc);
-  }
+  static int step(const StepCall& sc) { return EXCENV_BY_DTYPE(launch_step, MT, sc); }
+  static int sim(const SimCall& sc) { return EXCENV_BY_DTYPE(launch_sim, MT, sc); }
+  static int traj_gym(const TrajGymCall& gc) { return EXCENV_BY_DTYPE(launch_traj_gym, MT, gc); }
+  static int from_obs(const FromObsCall& fc) { return EXCENV_BY_DTYPE(launch_from_obs, MT, fc); }
+  static int update_ref(const RefGenCall& rc) { return EXCENV_BY_DTYPE(launch_update_ref, MT, rc); }
+  static int random_state(const RandomStateCall& rc) { return EXCENV_BY_DTYPE(launch_random_state, MT, rc); }
+  static int observe(const ObserveCall& oc) { return EXCENV_BY_DTYPE(launch_observe, MT, oc); }
   static EnvVTable vtable() {
     return EnvVTable{MT<float>::S, MT<float>::A, MT<float>::O, MT<float>::P, &step, &sim, &traj_gym, &from_obs, &update_ref,
                      &random_state, &observe, &vjp_entry<MT>, &rew_vjp_entry<MT>, &step_vjp_entry<MT>, &step_jac_entry<MT>};

@@ -1,5 +1,3 @@
 // Step Jacobian kernel instantiations for one environment (its own translation unit so the six compile in parallel).
 #include "kernels_step_jac.hpp"
-namespace excenv {
-template <> int step_jac_entry<Pendulum>(const StepJacCall& jc) { return launch_step_jac_any<Pendulum>(jc); }
-}  // namespace excenv
+template int excenv::step_jac_entry<excenv::Pendulum>(const excenv::StepJacCall&);

@@ -1,5 +1,3 @@
 // Reverse-mode step kernel instantiations for one environment (its own translation unit so the six compile in parallel).
 #include "kernels_step_vjp.hpp"
-namespace excenv {
-template <> int step_vjp_entry<MassSpringDamper>(const StepVjpCall& sc) { return launch_step_vjp_any<MassSpringDamper>(sc); }
-}  // namespace excenv
+template int excenv::step_vjp_entry<excenv::MassSpringDamper>(const excenv::StepVjpCall&);

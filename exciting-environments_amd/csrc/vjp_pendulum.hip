@@ -1,5 +1,3 @@
 // Reverse-mode kernel instantiations for one environment (its own translation unit so the six compile in parallel).
 #include "kernels_vjp.hpp"
-namespace excenv {
-template <> int vjp_entry<Pendulum>(const VjpCall& vc) { return launch_vjp_any<Pendulum>(vc); }
-}  // namespace excenv
+template int excenv::vjp_entry<excenv::Pendulum>(const excenv::VjpCall&);

@@ -12,7 +12,7 @@ import ctypes
 import torch
 
 from . import _native
-from ._vjp import _leaf_list
+from ._reverse import _leaf_list, unsupported
 
 
 class LinearizeMixin:
@@ -21,11 +21,7 @@ class LinearizeMixin:
 
     def _linearize_unsupported(self):
         """The reason this environment's configuration has no linearisation, or None. Touches no device."""
-        if getattr(self.env_properties, "saturated", False):
-            return "the saturated PMSM has no reverse mode, and the Jacobian rows are its products"
-        if self._props_for(self.env_properties, self.batch_size)[1]:
-            return "per-environment property arrays have no reverse mode (broadcast properties only)"
-        return None
+        return unsupported(self, saturated="the saturated PMSM has no reverse mode, and the Jacobian rows are its products")
 
     def _jac_rows(self, rows):
         """-> (row kind id, R)"""

@@ -16,7 +16,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _native
-from ._vjp import _leaf_list
+from ._reverse import _leaf_list, cotangent, count_control, opt_ptrs, unsupported
 
 
 class _Step(torch.autograd.Function):
@@ -78,11 +78,7 @@ class StepVjpMixin:
 
     def _step_vjp_unsupported(self):
         """The reason this environment's configuration has no reverse-mode step, or None."""
-        if getattr(self.env_properties, "saturated", False):
-            return "the saturated PMSM has no reverse mode"
-        if self._props_for(self.env_properties, self.batch_size)[1]:
-            return "per-environment property arrays have no reverse mode (broadcast properties only)"
-        return None
+        return unsupported(self)
 
     def _step_differentiable(self, state, action, gym: bool):
         what = "vmap_gym_step" if gym else "vmap_step"
@@ -138,47 +134,32 @@ class StepVjpMixin:
         cotangent); packed: the forward's packed properties."""
         B, S, A, OW = self.batch_size, self.physical_state_dim, self.action_dim, self._obs_dim()
         dt, dev = self.dtype, self.device
-
-        def dense(g, shape):
-            g = g.detach()
-            if g.device != dev or g.dtype != dt:
-                g = g.to(device=dev, dtype=dt)
-            assert g.numel() == B * (shape[1] if len(shape) > 1 else 1) and g.shape[0] == B, \
-                f"cotangent of shape {tuple(g.shape)}, expected {shape}"
-            return g.reshape(shape).contiguous()
-
         action = self._t(action.detach(), (B, A))
         if action.data_ptr() % 16:  # a contiguous slice that starts inside a 16-byte piece: rows are read as 16-byte pieces
             action = action.clone()
-        if g_obs is not None:
-            g_obs = dense(g_obs, (B, OW))
-            if g_obs.data_ptr() % 16:  # rows are read as 16-byte pieces; the [B] cotangents are read one element per lane
-                g_obs = g_obs.clone()
+        if g_obs is not None:  # rows are read as 16-byte pieces; the [B] cotangents are read one element per lane
+            g_obs = cotangent(g_obs, dev, dt, (B, OW))
         if g_state is not None:
-            g_state = [None if g is None else dense(g, (B,)) for g in g_state]
+            g_state = [None if g is None else cotangent(g, dev, dt, (B,), align=False) for g in g_state]
         if g_reward is not None and not self.control_state:
             g_reward = None  # without controlled fields the reward is a constant
-        g_reward = None if g_reward is None else dense(g_reward, (B,))
+        g_reward = None if g_reward is None else cotangent(g_reward, dev, dt, (B,), align=False)
         props, _keep = packed if packed is not None else self._props_for(self.env_properties, B)
-        control = None
-        if self.control_state:
-            if g_reward is not None:
-                control = _native.make_control([self.STATE_FIELDS.index(n) for n in self.control_state], list(refs))
-            else:
-                control = _native.Control()
-                control.n_control = len(self.control_state)
+        if g_reward is not None:  # set with controlled fields only
+            control = _native.make_control([self.STATE_FIELDS.index(n) for n in self.control_state], list(refs))
+        else:
+            control = count_control(self)
         al = 16 // (4 if dt == torch.float32 else 8)
         Bp = (B + al - 1) // al * al  # every leaf and the action block 16-byte aligned inside the single allocation
         buf = torch.empty(S * Bp + B * A, dtype=dt, device=dev)
         gs = [buf[j * Bp: j * Bp + B] for j in range(S)]
         ga = buf[S * Bp:].view(B, A)
-        opt_ptrs = None if g_state is None else (ctypes.c_void_p * S)(*[None if t is None else t.data_ptr() for t in g_state])
         self.last_step_vjp_cotangents = {"obs": g_obs is not None,
                                          "state": [False] * S if g_state is None else [g is not None for g in g_state],
                                          "reward": g_reward is not None}
         _native._launch("excenv_step_vjp", buf, "vmap_step_vjp", self.ENV_ID, self._solver.id, _native.dtype_id(dt), B,
                         ctypes.byref(props), _native._ref(control), float(self.tau), _native._ptrs(st_in), action.data_ptr(),
-                        _native._ptrs(st_out), _native._ptr(g_obs), opt_ptrs, _native._ptr(g_reward), _native._ptrs(gs),
+                        _native._ptrs(st_out), _native._ptr(g_obs), opt_ptrs(g_state), _native._ptr(g_reward), _native._ptrs(gs),
                         ga.data_ptr(), _native._ref(self.launch_opts))
         self.last_step_vjp_launch = _native.last_launch()
         return ga, gs

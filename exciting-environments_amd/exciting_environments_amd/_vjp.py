@@ -18,19 +18,9 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _native
+from ._reverse import _leaf_list, cotangent, count_control, opt_ptrs, unsupported
 
 _EM, _LM = _native.LAYOUT_ENV_MAJOR, _native.LAYOUT_LANE_MAJOR
-
-
-def _leaf_list(x, fields):
-    """State / PhysicalState pytree or a sequence -> list of leaves (None where absent)."""
-    if x is None:
-        return None
-    x = getattr(x, "physical_state", x)
-    if isinstance(x, (list, tuple)):
-        assert len(x) == len(fields), f"expected {len(fields)} state leaves"
-        return list(x)
-    return [getattr(x, n, None) for n in fields]
 
 
 class _SimAhead(torch.autograd.Function):
@@ -102,11 +92,7 @@ class TrajectoryVjpMixin:
             return f"sim_ahead_semantics={self.sim_ahead_semantics!r} has no reverse mode (use 'ahead' or 'step')"
         if self.traj_layout != "lane_major":
             return f"traj_layout={self.traj_layout!r} has no reverse mode (the 'env_major' and 'tiled' layouts are forward only)"
-        if getattr(self.env_properties, "saturated", False):
-            return "the saturated PMSM has no reverse mode"
-        if self._props_for(self.env_properties, self.batch_size)[1]:
-            return "per-environment property arrays have no reverse mode (broadcast properties only)"
-        return None
+        return unsupported(self)
 
     # excenv_last_launch() of the most recent reverse launch, read on the thread that enqueued it: the C string is per thread, and
     # autograd runs backward on a thread of its own, where the caller's excenv_last_launch() still names the forward
@@ -202,13 +188,7 @@ class TrajectoryVjpMixin:
 
     def _lane_major(self, g, shape, strides):
         """g as a tensor of `shape` whose memory is lane-major (`strides`): itself when it is, else a copy."""
-        g = g if (g.device == self.device and g.dtype == self.dtype) else g.to(device=self.device, dtype=self.dtype)
-        assert tuple(g.shape) == shape, f"cotangent of shape {tuple(g.shape)}, expected {shape}"
-        if tuple(g.stride()) == strides and g.data_ptr() % 16 == 0:
-            return g
-        buf = torch.empty_strided(shape, strides, dtype=self.dtype, device=self.device)
-        buf.copy_(g)
-        return buf
+        return cotangent(g, self.device, self.dtype, shape, strides)
 
     def _sim_ahead_vjp_launch(self, traj, actions, obs_stepsize, action_stepsize, g_obs, g_states, g_last, param_idx=None,
                               packed=None):
@@ -241,10 +221,7 @@ class TrajectoryVjpMixin:
         if g_last is not None:
             g_last = [None if g is None else self._lane_major(g, (B,), (1,)) for g in g_last]
         props, keep = packed if packed is not None else self._props_for(self.env_properties, B)
-        control = None
-        if self.control_state:
-            control = _native.Control()
-            control.n_control = len(self.control_state)
+        control = count_control(self)
         grad_actions = torch.empty((K, A, B), dtype=dt, device=dev)
         grad_in = torch.empty((S, (B + 3) // 4 * 4), dtype=dt, device=dev)  # every leaf 16-byte aligned
         gs = [grad_in[j, :B] for j in range(S)]
@@ -253,7 +230,6 @@ class TrajectoryVjpMixin:
         ws_bytes = _native.lib().excenv_sim_ahead_vjp_workspace_bytes_for(self.ENV_ID, self._solver.id, _native.dtype_id(dt), B, K, sub,
                                                                           self._semantics_id, a_layout)
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes > 0 else None
-        opt_ptrs = lambda ts: None if ts is None else (ctypes.c_void_p * S)(*[None if t is None else t.data_ptr() for t in ts])
         args = (self.ENV_ID, self._solver.id,
                 _native.dtype_id(dt), B, K, sub, ctypes.byref(props), _native._ref(control), float(obs_stepsize),
                 float(self.tau), actions.data_ptr() if K > 0 else None, a_layout, _native._ptrs(traj), _native._ptr(g_obs),

@@ -82,3 +82,18 @@ def twin_step_grads(tw, g_obs=None, g_state=None, g_rew=None):
     gr = torch.autograd.grad(loss, [act] + lv, allow_unused=True, retain_graph=True)
     z = lambda g, like: np.zeros(tuple(like.shape)) if g is None else g.numpy()
     return z(gr[0], act), [z(g, s) for g, s in zip(gr[1:], lv)]
+
+
+def check_fp32_excluded_share():
+    """The fp32 comparisons of tests/test_gpu_step_vjp.py and tests/test_gpu_linearize.py leave out the environments the twin sees
+    closer than KINK_MARGIN to a kink: on their inputs (step_inputs, fp32-representable values, every model and solver) that is at
+    most KINK_CAP of them."""
+    from helpers_vjp import CASES, KINK_CAP, KINK_MARGIN, SOLVERS
+
+    for env_name, deadtime in CASES:
+        spec, st, act = step_inputs(env_name, deadtime, B0, np_dtype=np.float32)
+        for solver in SOLVERS:
+            kd = twin_step(env_name, spec, solver, [v.astype(np.float64) for v in st], act.astype(np.float64))[5]
+            excluded = 0.0 if kd is None else float((kd.numpy() < KINK_MARGIN).mean())
+            print(f"{env_name} dead={deadtime} {solver}: excluded {excluded:.4f}")
+            assert excluded <= KINK_CAP

@@ -451,14 +451,9 @@ def test_headline_loop_stays_inside_the_instruction_cache():
     """Guard rail (tools/loop_code_size.py): the K loop of the headline kernel — PMSM Euler fp32, V = 4, two unrolled solver
     steps x 4 environments per lane — is the largest piece of code that must stay resident in the 64 KB instruction cache for
     the headline number; anything that grows it past 60 KB fails here, at build time, instead of showing up as a slow GPU run."""
-    import importlib.util
+    import helpers_budget
 
-    spec = importlib.util.spec_from_file_location("loop_code_size", os.path.join(ROOT, "tools", "loop_code_size.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    if not os.path.exists(mod.OBJDUMP):
-        pytest.skip("llvm-objdump not available")
-    spans = mod.loop_spans()
+    mod, spans = helpers_budget.tool(), helpers_budget.spans("sim_ahead")
     assert mod.HEADLINE in spans, "headline instantiation missing from the library"
     loop, size = spans[mod.HEADLINE]
     assert 8 * 1024 < loop <= 60 * 1024, f"headline K loop is {loop} bytes"
@@ -472,14 +467,9 @@ def test_trajectory_kernels_do_not_spill():
     `s_waitcnt vmcnt(0)`, i.e. behind every outstanding trajectory store (the register-ring kernel lost 0.6 of 7.7 ms to 18 spilled
     registers; a non-inlined lambda costs a stack frame the same way). The headline kernels use no scratch memory at all; the
     register-ring kernels at most a few bytes that only cold paths touch."""
-    import importlib.util
+    import helpers_budget
 
-    spec = importlib.util.spec_from_file_location("loop_code_size", os.path.join(ROOT, "tools", "loop_code_size.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    if not (os.path.exists(mod.OBJDUMP) and os.path.exists(mod.READELF)):
-        pytest.skip("llvm-objdump / llvm-readelf not available")
-    res = mod.kernel_resources()
+    mod, res = helpers_budget.tool(), helpers_budget.budget("")[0]
     assert res[mod.HEADLINE]["scratch"] == 0 and res[mod.HEADLINE]["vgpr"] <= 256
     ring = {k: v for k, v in res.items() if "sim_ahead_emr_kernel" in k}
     assert len(ring) >= 60

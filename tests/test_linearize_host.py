@@ -2,7 +2,6 @@
 loop budget, excenv_step_jacobian rejects by code and name what it does not do before any launch, excenv_step_jacobian_bytes is the
 formula of DESIGN.md §4.10, and the Python methods refuse by name on CPU environments."""
 import ctypes
-import importlib.util
 import itertools
 import os
 import re
@@ -11,18 +10,12 @@ import pytest
 import torch
 
 from exciting_environments_amd import EnvironmentRegistry, _native
+from helpers_budget import budget, check_budget
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 i64, i32, vp, dbl = ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_double
 EINVAL, ENULL, EUNSUPPORTED = -1, -2, -4
 MODELS = ["Pendulum", "MassSpringDamper", "CartPole", "Acrobot", "FluidTank", "Pmsm"]
-
-
-def _tool():
-    spec = importlib.util.spec_from_file_location("loop_code_size", os.path.join(ROOT, "tools", "loop_code_size.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
 
 
 def test_header_declares_and_library_exports_the_entry_points():
@@ -39,26 +32,16 @@ def test_header_declares_and_library_exports_the_entry_points():
 def test_step_jac_kernels_exist_and_stay_within_the_register_scratch_and_loop_budget():
     """tools/loop_code_size.py on the built library: the 36 instantiations (six models x three solvers x two element types) are all
     there, use no scratch memory and at most 256 vector registers, and their row loop is under 60 KB."""
-    mod = _tool()
-    if not (os.path.exists(mod.OBJDUMP) and os.path.exists(mod.READELF)):
-        pytest.skip("llvm-objdump / llvm-readelf not available")
-    every = mod.kernel_resources()
-    res = {k: v for k, v in every.items() if "step_jac_kernel" in k}
+    res, spans = budget("step_jac_kernel")
     for other in ("step_vjp_kernel", "rew_vjp_kernel", "sim_ahead_vjp_kernel"):  # what the other host tests count kernels by
         assert not [k for k in res if other in k], other
-    spans = mod.loop_spans(match="step_jac_kernel")
     for model, t, solver in itertools.product(MODELS, "fd", (0, 1, 2)):
         key = f"step_jac_kernelINS_{len(model)}{model}I{t}EE{t}Li{solver}EE"
         hit = [k for k in res if key in k]
         assert len(hit) == 1, (key, hit)
         print(f"{model} {'fp32' if t == 'f' else 'fp64'} solver {solver}: {res[hit[0]]} loop {spans[hit[0]][0]} B of {spans[hit[0]][1]} B")
     assert len(res) == 36, len(res)
-    over = {k: v for k, v in res.items() if v["scratch"] != 0 or v["vgpr"] > 256}
-    assert not over, over
-    assert len(spans) == len(res)
-    worst = max(spans.items(), key=lambda kv: kv[1][0])
-    print("largest loop:", worst, "largest kernel:", max(v[1] for v in spans.values()))
-    assert 0 < worst[1][0] < 60 * 1024
+    assert 0 < check_budget(res, spans)[1][0]
     assert all(v[0] > 0 for v in spans.values()), "the row loop is a run-time loop in every instantiation"
 
 
@@ -186,15 +169,6 @@ def test_python_refuses_by_name_what_a_linearisation_does_not_do():
 def test_the_fp32_inputs_keep_the_excluded_share_under_the_cap():
     """tests/test_gpu_linearize.py compares fp32 Jacobians on the environments the twin sees at least KINK_MARGIN from a kink: on
     its inputs (helpers_step_vjp.step_inputs, fp32-representable values, every model and solver) at most KINK_CAP of them are left out."""
-    import numpy as np
+    from helpers_step_vjp import check_fp32_excluded_share
 
-    from helpers_step_vjp import B0, step_inputs, twin_step
-    from helpers_vjp import CASES, KINK_CAP, KINK_MARGIN, SOLVERS
-
-    for env_name, deadtime in CASES:
-        spec, st, act = step_inputs(env_name, deadtime, B0, np_dtype=np.float32)
-        for solver in SOLVERS:
-            kd = twin_step(env_name, spec, solver, [v.astype(np.float64) for v in st], act.astype(np.float64))[5]
-            excluded = 0.0 if kd is None else float((kd.numpy() < KINK_MARGIN).mean())
-            print(f"{env_name} dead={deadtime} {solver}: excluded {excluded:.4f}")
-            assert excluded <= KINK_CAP
+    check_fp32_excluded_share()

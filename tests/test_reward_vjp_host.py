@@ -3,7 +3,6 @@ table, rejections before any launch, the CPU `vmap_reward_vjp` (torch autograd o
 the fp64 oracle on the very inputs the GPU tests use (tests/helpers_reward_vjp.py: the exclusion cap and the branch coverage are
 asserted here on those arrays), and the built rew_vjp_kernel instantiations use no scratch."""
 import ctypes
-import importlib.util
 import os
 import re
 
@@ -15,6 +14,7 @@ import oracle
 from conftest import ENV_NAMES
 from exciting_environments_amd import _native
 from helpers import make_env
+from helpers_budget import budget
 from helpers_reward_vjp import (NARROW_B, ROWS, check_coverage_and_cap, control_sets, expected_reads, make_states, oracle_grads,
                                 rel_dist, reward_inputs, tensor, to_np, wide_b)
 
@@ -172,12 +172,7 @@ def test_cpu_reward_vjp_takes_a_two_dimensional_cotangent_and_ignores_the_switch
 
 # ---------------------------------------------------------------------------------------------------------------- 5
 def test_rew_vjp_kernels_use_no_scratch():
-    spec = importlib.util.spec_from_file_location("loop_code_size", os.path.join(ROOT, "tools", "loop_code_size.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    if not (os.path.exists(mod.OBJDUMP) and os.path.exists(mod.READELF)):
-        pytest.skip("llvm-objdump / llvm-readelf not available")
-    res = {k: v for k, v in mod.kernel_resources().items() if "rew_vjp_kernel" in k}
+    res = budget("rew_vjp_kernel")[0]
     assert len(res) == 6 * 2 * 2, len(res)  # six models x two element types x two forms
     assert not any("sim_ahead_vjp_kernel" in k for k in res)
     over = {k: v for k, v in res.items() if v["scratch"] != 0}

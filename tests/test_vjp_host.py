@@ -2,7 +2,6 @@
 before any launch, the built sim_ahead_vjp_kernel instantiations stay within the register / scratch / loop-size budget, and the
 Python switch defaults to off."""
 import ctypes
-import importlib.util
 import os
 import re
 
@@ -10,17 +9,11 @@ import pytest
 import torch
 
 from exciting_environments_amd import EnvironmentRegistry, _native
+from helpers_budget import budget, check_budget
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 i64, i32, vp, dbl = ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_double
 EINVAL, ENULL, EUNSUPPORTED = -1, -2, -4
-
-
-def _tool():
-    spec = importlib.util.spec_from_file_location("loop_code_size", os.path.join(ROOT, "tools", "loop_code_size.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
 
 
 def test_header_declares_and_library_exports_the_vjp_entry_points():
@@ -108,21 +101,10 @@ def test_unsupported_combinations_are_rejected_before_any_launch():
 def test_vjp_kernels_stay_within_the_register_scratch_and_loop_budget():
     """tools/loop_code_size.py on the built library: every sim_ahead_vjp_kernel instantiation uses no scratch memory and at most 256
     vector registers (accumulation registers included), and its largest loop is below 60 KB — the bound of the headline test."""
-    mod = _tool()
-    if not (os.path.exists(mod.OBJDUMP) and os.path.exists(mod.READELF)):
-        pytest.skip("llvm-objdump / llvm-readelf not available")
-    res = {k: v for k, v in mod.kernel_resources().items() if "sim_ahead_vjp_kernel" in k}
+    res, spans = budget("sim_ahead_vjp_kernel")
     # six models x three solvers x two semantics x two dtypes, one environment per lane; the wide forms on top
     assert len(res) >= 72 + 30, len(res)
-    over = {k: v for k, v in res.items() if v["scratch"] != 0 or v["vgpr"] > 256}
-    for k, v in sorted(over.items()):
-        print(v, k)
-    assert not over, f"{len(over)} of {len(res)} instantiations over budget"
-    spans = {k: v for k, v in mod.loop_spans().items() if "sim_ahead_vjp_kernel" in k}
-    assert len(spans) == len(res)
-    worst = max(spans.items(), key=lambda kv: kv[1][0])
-    print("largest loop:", worst)
-    assert worst[1][0] < 60 * 1024
+    check_budget(res, spans)
 
 
 def test_differentiable_defaults_to_false():

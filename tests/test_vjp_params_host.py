@@ -2,7 +2,6 @@
 launch, the PGRAD instantiations of sim_ahead_vjp_kernel exist and stay within the register / scratch / loop-size budget, the plain
 instantiations kept the register counts of the commit before (tests/golden/vjp_resources_parent.json), and the form rule."""
 import ctypes
-import importlib.util
 import json
 import os
 import re
@@ -13,18 +12,12 @@ import pytest
 import torch
 
 from exciting_environments_amd import EnvironmentRegistry, _native
+from helpers_budget import budget, check_budget
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 i64, i32, vp, dbl = ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_double
 EINVAL, ENULL, EUNSUPPORTED = -1, -2, -4
 ENVS = {"pendulum": 0, "mass_spring_damper": 1, "cartpole": 2, "acrobot": 3, "fluid_tank": 4, "pmsm": 5}
-
-
-def _tool():
-    spec = importlib.util.spec_from_file_location("loop_code_size", os.path.join(ROOT, "tools", "loop_code_size.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
 
 
 def test_header_declares_and_library_exports_the_new_entry_points():
@@ -139,10 +132,7 @@ def _args(sym):
 def test_pgrad_instantiations_exist_within_the_budget_and_the_plain_ones_kept_their_registers():
     from helpers_vjp_params import vjp_pgrad_wide_ok
 
-    mod = _tool()
-    if not (os.path.exists(mod.OBJDUMP) and os.path.exists(mod.READELF)):
-        pytest.skip("llvm-objdump / llvm-readelf not available")
-    res = {k: v for k, v in mod.kernel_resources().items() if "sim_ahead_vjp_kernel" in k}
+    res, spans = budget("sim_ahead_vjp_kernel")
     pgrad = {k: v for k, v in res.items() if PGRAD.match(k)}
     plain = {k: v for k, v in res.items() if PLAIN.match(k)}
     assert len(pgrad) + len(plain) == len(res)
@@ -156,15 +146,7 @@ def test_pgrad_instantiations_exist_within_the_budget_and_the_plain_ones_kept_th
     assert wide == want
     for e in ("pendulum", "mass_spring_damper", "fluid_tank"):  # the three small models keep their wide form for all solvers
         assert all(vjp_pgrad_wide_ok(e, elem, s) for elem in (4, 8) for s in ("euler", "rk4", "tsit5"))
-    over = {k: v for k, v in pgrad.items() if v["scratch"] != 0 or v["vgpr"] > 256}
-    for k, v in sorted(over.items()):
-        print(v, k)
-    assert not over, f"{len(over)} of {len(pgrad)} PGRAD instantiations over budget"
-    spans = {k: v for k, v in mod.loop_spans().items() if PGRAD.match(k)}
-    assert len(spans) == len(pgrad)
-    worst = max(spans.items(), key=lambda kv: kv[1][0])
-    print("largest PGRAD loop:", worst, "most registers:", max(v["vgpr"] for v in pgrad.values()))
-    assert worst[1][0] < 60 * 1024
+    check_budget(pgrad, {k: v for k, v in spans.items() if PGRAD.match(k)})
     # PGRAD == false: the instantiations of the commit before, register for register (their symbols gained the flag only)
     gold = json.load(open(os.path.join(ROOT, "tests", "golden", "vjp_resources_parent.json")))
     gold.pop("_comment")

@@ -21,44 +21,47 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "exciting-environments_amd", "exciting_environments_amd", "lib", "libexcenv_hip.so")
 OBJDUMP = "/opt/rocm/lib/llvm/bin/llvm-objdump"
+READELF = "/opt/rocm/lib/llvm/bin/llvm-readelf"
 HEADLINE = "_ZN6excenv16sim_ahead_kernelINS_4PmsmIfEEfLi0ELb1ELb0ELi4ELi1ELb0ELb0ELb0ELi256EEEvNS_7SimArgsIT0_T_EE"
+
+
+def _code_objects(lib, cmd):
+    """The output of `cmd + [code object]` for every device code object packed into the library"""
+    with tempfile.TemporaryDirectory() as td:
+        so = os.path.join(td, "lib.so")
+        shutil.copy(lib, so)
+        subprocess.run([OBJDUMP, "--offloading", so], check=True, cwd=td, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+        for elf in sorted(glob.glob(os.path.join(td, "lib.so.*amdgcn*"))):
+            yield subprocess.run(cmd + [elf], check=True, capture_output=True, text=True).stdout
 
 
 def loop_spans(lib=LIB, match="sim_ahead"):
     """{kernel symbol: (largest backward-branch span in bytes, kernel size in bytes)} for the kernels whose symbol contains `match`
     (default: the trajectory kernels). A kernel without a loop has span 0."""
     out = {}
-    with tempfile.TemporaryDirectory() as td:
-        so = os.path.join(td, "lib.so")
-        shutil.copy(lib, so)
-        subprocess.run([OBJDUMP, "--offloading", so], check=True, cwd=td, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-        for elf in sorted(glob.glob(os.path.join(td, "lib.so.*amdgcn*"))):
-            dis = subprocess.run([OBJDUMP, "-d", "--no-show-raw-insn", elf], check=True, capture_output=True, text=True).stdout
-            sym, first, last, span = None, None, None, 0
-            for line in dis.splitlines():
-                m = re.match(r"^([0-9a-f]+) <(\S+)>:", line)
-                if m:
-                    if sym and match in sym:
-                        out[sym] = (span, last - first)
-                    sym, first, last, span = m.group(2), int(m.group(1), 16), int(m.group(1), 16), 0
-                    continue
-                m = re.match(r"^\s+(s_c?branch\S*)\s.*?//\s*([0-9A-Fa-f]+):", line) or re.match(r"^\s+(\S+).*//\s*([0-9A-Fa-f]+):", line)
-                if not m or sym is None:
-                    continue
-                addr = int(m.group(2), 16)
-                last = max(last, addr)
-                if m.group(1).startswith(("s_branch", "s_cbranch")):
-                    t = re.search(r"<[^>]*\+0x([0-9a-fA-F]+)>", line)
-                    if t:
-                        target = first + int(t.group(1), 16)
-                        if target <= addr:
-                            span = max(span, addr - target)
-            if sym and match in sym:
-                out[sym] = (span, last - first)
+    for dis in _code_objects(lib, [OBJDUMP, "-d", "--no-show-raw-insn"]):
+        sym, first, last, span = None, None, None, 0
+        for line in dis.splitlines():
+            m = re.match(r"^([0-9a-f]+) <(\S+)>:", line)
+            if m:
+                if sym and match in sym:
+                    out[sym] = (span, last - first)
+                sym, first, last, span = m.group(2), int(m.group(1), 16), int(m.group(1), 16), 0
+                continue
+            m = re.match(r"^\s+(s_c?branch\S*)\s.*?//\s*([0-9A-Fa-f]+):", line) or re.match(r"^\s+(\S+).*//\s*([0-9A-Fa-f]+):", line)
+            if not m or sym is None:
+                continue
+            addr = int(m.group(2), 16)
+            last = max(last, addr)
+            if m.group(1).startswith(("s_branch", "s_cbranch")):
+                t = re.search(r"<[^>]*\+0x([0-9a-fA-F]+)>", line)
+                if t:
+                    target = first + int(t.group(1), 16)
+                    if target <= addr:
+                        span = max(span, addr - target)
+        if sym and match in sym:
+            out[sym] = (span, last - first)
     return out
-
-
-READELF = "/opt/rocm/lib/llvm/bin/llvm-readelf"
 
 
 def kernel_resources(lib=LIB):
@@ -66,25 +69,20 @@ def kernel_resources(lib=LIB):
     notes. A trajectory kernel that starts to spill reloads its registers behind `s_waitcnt vmcnt(0)`, i.e. behind every
     outstanding trajectory store (kernels_emr.hpp: 7.7 -> 7.1 ms when the last spills went): worth failing the build for."""
     out = {}
-    with tempfile.TemporaryDirectory() as td:
-        so = os.path.join(td, "lib.so")
-        shutil.copy(lib, so)
-        subprocess.run([OBJDUMP, "--offloading", so], check=True, cwd=td, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-        for elf in sorted(glob.glob(os.path.join(td, "lib.so.*amdgcn*"))):
-            notes = subprocess.run([READELF, "--notes", elf], check=True, capture_output=True, text=True).stdout
-            cur = {}
-            for line in notes.splitlines():
-                m = re.match(r"\s*-?\s*\.(name|private_segment_fixed_size|vgpr_count|sgpr_count):\s*(\S+)", line)
-                if not m:
-                    continue
-                k, v = m.group(1), m.group(2).strip("'\"")
-                if k == "name" and not v.startswith("_Z"):
-                    continue  # argument names
-                cur[k] = v
-                if all(x in cur for x in ("name", "private_segment_fixed_size", "vgpr_count", "sgpr_count")):
-                    out[cur["name"]] = {"scratch": int(cur["private_segment_fixed_size"]), "vgpr": int(cur["vgpr_count"]),
-                                        "sgpr": int(cur["sgpr_count"])}
-                    cur = {}
+    for notes in _code_objects(lib, [READELF, "--notes"]):
+        cur = {}
+        for line in notes.splitlines():
+            m = re.match(r"\s*-?\s*\.(name|private_segment_fixed_size|vgpr_count|sgpr_count):\s*(\S+)", line)
+            if not m:
+                continue
+            k, v = m.group(1), m.group(2).strip("'\"")
+            if k == "name" and not v.startswith("_Z"):
+                continue  # argument names
+            cur[k] = v
+            if all(x in cur for x in ("name", "private_segment_fixed_size", "vgpr_count", "sgpr_count")):
+                out[cur["name"]] = {"scratch": int(cur["private_segment_fixed_size"]), "vgpr": int(cur["vgpr_count"]),
+                                    "sgpr": int(cur["sgpr_count"])}
+                cur = {}
     return out
 
 
