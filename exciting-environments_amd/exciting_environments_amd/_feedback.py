@@ -1,0 +1,140 @@
+"""Closed-loop trajectories: `vmap_sim_ahead_feedback` runs a whole horizon in ONE persistent launch of sim_feedback_kernel through
+`excenv_sim_feedback` (include/excenv.h), with every action computed inside the kernel from the observation row it has just saved:
+affine output feedback, optional integral action, optional feedforward row. Mixed into `CoreEnvironment`
+(core_env.py).
+
+The rows are the post-processed states `vmap_step` carries ("step" semantics), so the returned observations, states and last state are
+bit for bit what `vmap_sim_ahead` returns under `sim_ahead_semantics = "step"` for the returned actions. Nothing here records a graph:
+there is no reverse mode through the policy."""
+from __future__ import annotations
+
+import ctypes
+import math
+
+import torch
+
+from . import _native
+from ._trajectory import _lane_major_leaves, _lane_major_obs
+
+
+class FeedbackMixin:
+    # excenv_last_launch() of the most recent excenv_sim_feedback launch of this environment
+    last_feedback_launch = ""
+
+    def _lane_major_gain(self, gain, what):
+        """[A, OW] (one gain set for all) or [B, A, OW] (one per environment) -> (tensor over [A][OW][Bg] memory, Bg)"""
+        B, A, OW = self.batch_size, self.action_dim, self._obs_dim()
+        gain = torch.as_tensor(gain).detach()
+        assert tuple(gain.shape) in ((A, OW), (B, A, OW)), (
+            f"{what} needs to be of shape (action_dim, obs_dim) or (batch_size, action_dim, obs_dim) which is {(A, OW)} or "
+            f"{(B, A, OW)}, but {tuple(gain.shape)} is given")
+        if gain.device != self.device or gain.dtype != self.dtype:
+            gain = gain.to(device=self.device, dtype=self.dtype)
+        if gain.ndim == 2:
+            return gain.contiguous(), 1
+        if B > 0 and tuple(gain.stride()) != (1, OW * B, B):
+            gain = gain.permute(1, 2, 0).contiguous().permute(2, 0, 1)
+        return gain, B
+
+    def vmap_sim_ahead_feedback(self, init_state, gain, n_actions, obs_stepsize, action_stepsize, feedforward=None,
+                                integral_gain=None, integrator_state=None, clip=(-1.0, 1.0)):
+        """Closed-loop trajectories of all batch_size environments in one kernel launch -> (observations [B, N+1, OW],
+        states with leaves [B, N+1], last_state with leaves [B], actions [B, K, A], z [B, A] or None), K = n_actions action rows
+        of substeps = action_stepsize / obs_stepsize solver steps each, N = K * substeps.
+
+        At every action row k the kernel reads the observation row it has just saved (row k * substeps, the normalised references
+        of `control_state` included: what `generate_observation` builds) and applies, per action component q,
+            a[k, q] = clamp(feedforward[k, q] + z[q] + sum_o gain[q, o] * obs[o])
+            z[q]    = clamp(z[q] + action_stepsize * sum_o integral_gain[q, o] * obs[o])
+        (sums as fused multiply-adds in column order; z only with `integral_gain`, its clamp is the anti-windup). The normalised
+        action is held for `substeps` steps of `vmap_step`'s arithmetic.
+
+        gain, integral_gain: [A, OW] (one gain set for every environment) or [B, A, OW] (one per environment).
+        feedforward: [B, K, A] or None; a view from `env.new_actions_buffer(K)` is read in place, anything else is copied into one.
+        n_actions: K; may be None when `feedforward` gives it. integrator_state: the initial z [B, A] (None: zeros).
+        clip: (low, high) for both clamps, None: no clamp. References of the controlled fields come from `init_state.reference`.
+
+        The returned tensors are views of freshly allocated lane-major memory; `states` is None with
+        `env.store_state_trajectory = False`. `vmap_generate_rew_trunc_term_ahead(states, actions)` gives the gym outputs.
+        Refused by name (ValueError): trajectory layouts other than "lane_major", `sim_ahead_semantics ==
+        "ahead_accumulated_t"`, and `env.differentiable` with an input that requires grad: the outputs carry no graph."""
+        if self.traj_layout != "lane_major":
+            raise ValueError(f"vmap_sim_ahead_feedback: traj_layout={self.traj_layout!r}: the closed-loop kernel writes the "
+                             "'lane_major' layout only")
+        if self.sim_ahead_semantics == "ahead_accumulated_t":
+            raise ValueError("vmap_sim_ahead_feedback: sim_ahead_semantics='ahead_accumulated_t': a closed loop reads the saved row "
+                             "of every action, its trajectory is a chain of steps ('step' semantics) on every setting")
+        tensors = [gain, integral_gain, feedforward, integrator_state]
+        tensors += [getattr(init_state.physical_state, n) for n in self.STATE_FIELDS]
+        if self.differentiable and torch.is_grad_enabled() and (
+                self._param_leaves() or any(isinstance(t, torch.Tensor) and t.requires_grad for t in tensors)):
+            raise ValueError("vmap_sim_ahead_feedback: env.differentiable with an input that requires grad: there is no reverse mode "
+                             "through the policy; detach the inputs or set env.differentiable = False")
+        B, S, A, OW = self.batch_size, self.physical_state_dim, self.action_dim, self._obs_dim()
+        dt, dev = self.dtype, self.device
+        assert obs_stepsize <= action_stepsize, "The action stepsize should be greater or equal to the observation stepsize."
+        phys_shape = self._phys_shape(init_state.physical_state)
+        assert phys_shape == (B, S), (
+            "The initial physical state needs to be of shape (batch_size, physical_state_dim,) which is "
+            + f"{(B, S)}, but {phys_shape} is given")
+        if feedforward is not None:
+            feedforward = torch.as_tensor(feedforward).detach()
+            assert feedforward.ndim == 3 and feedforward.shape[0] == B and feedforward.shape[2] == A, (
+                "The feedforward needs to have three dimensions: (batch_size, n_actions, action_dim) which is "
+                + f"{(B, n_actions, A)}, but {tuple(feedforward.shape)} is given")
+            assert n_actions is None or int(n_actions) == feedforward.shape[1], (
+                f"n_actions is {n_actions}, but the feedforward has {feedforward.shape[1]} action rows")
+            n_actions = feedforward.shape[1]
+        assert n_actions is not None and int(n_actions) >= 0, "n_actions is needed where no feedforward gives it"
+        K = int(n_actions)
+        sub = self._n_substeps(K, obs_stepsize, action_stepsize)
+        N = K * sub
+        lo, hi = (-math.inf, math.inf) if clip is None else (float(clip[0]), float(clip[1]))
+        assert lo <= hi, f"clip needs to be (low, high) with low <= high, but {clip} is given"
+        g, Bg = self._lane_major_gain(gain, "The gain")
+        gi = None
+        if integral_gain is not None:
+            gi, Bgi = self._lane_major_gain(integral_gain, "The integral gain")
+            if Bgi != Bg:  # one gain_batch for both: the broadcast one is repeated
+                if Bg == 1:
+                    g, Bg = g[:, :, None].expand(A, OW, B).contiguous().permute(2, 0, 1), B
+                else:
+                    gi = gi[:, :, None].expand(A, OW, B).contiguous().permute(2, 0, 1)
+        z_in = None
+        if integrator_state is not None:
+            assert integral_gain is not None, "integrator_state without integral_gain"
+            z_in = torch.as_tensor(integrator_state).detach()
+            assert tuple(z_in.shape) == (B, A), (
+                f"The integrator state needs to be of shape (batch_size, action_dim) which is {(B, A)}, but {tuple(z_in.shape)} is given")
+            z_in = z_in.to(device=dev, dtype=dt).t().contiguous()  # [A][B]
+        if feedforward is not None:
+            if feedforward.device != dev or feedforward.dtype != dt:
+                feedforward = feedforward.to(device=dev, dtype=dt)
+            if K > 0 and B > 0 and tuple(feedforward.stride()) != (1, A * B, B):
+                lane_major = self.new_actions_buffer(K)
+                lane_major.copy_(feedforward)
+                feedforward = lane_major
+
+        props, _keep = self._props_for(self.env_properties, B)
+        st_in = [self._t(getattr(init_state.physical_state, n), (B,)).detach() for n in self.STATE_FIELDS]
+        control, _refs = self._control(init_state, (B,))
+        new = lambda *shape: torch.empty(shape, dtype=dt, device=dev)
+        obs_buf = new(N + 1, OW, B)
+        st_buf = [new(N + 1, B) for _ in range(S)] if self.store_state_trajectory else None
+        last = [new(B) for _ in range(S)]
+        act_buf = new(K, A, B)
+        z_buf = new(A, B) if gi is not None else None
+        policy = _native.Feedback(g.data_ptr(), _native._ptr(gi), Bg, _native._ptr(feedforward) if K > 0 else None,
+                                  _native._ptr(z_in), _native._ptr(z_buf), lo, hi)
+        if B > 0:  # (an empty batch has no addresses to hand over)
+            _native._launch("excenv_sim_feedback", obs_buf, "vmap_sim_ahead_feedback", self.ENV_ID, self._solver.id,
+                            _native.dtype_id(dt), B, K, sub, ctypes.byref(props), _native._ref(control), float(obs_stepsize),
+                            float(self.tau), _native._ptrs(st_in), ctypes.byref(policy), obs_buf.data_ptr(), _native._ptrs(st_buf),
+                            _native._ptrs(last), act_buf.data_ptr() if K > 0 else None, _native._ref(self.launch_opts))
+            self.last_feedback_launch = _native.last_launch()
+        observations = _lane_major_obs(obs_buf, B, N + 1, OW)
+        states = None
+        if st_buf is not None:
+            states = self._traj_state(init_state, [_lane_major_leaves(b, 1, B, N + 1)[0] for b in st_buf], (B,), N)
+        last_state = self.State(self.PhysicalState(*last), init_state.PRNGKey, self._additions((B,), True), init_state.reference)
+        return observations, states, last_state, act_buf.permute(2, 0, 1), (z_buf.t() if z_buf is not None else None)

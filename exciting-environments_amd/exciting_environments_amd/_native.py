@@ -77,9 +77,17 @@ class Control(ctypes.Structure):
     ]
 
 
+class Feedback(ctypes.Structure):
+    """excenv_feedback_t: the affine feedback policy of excenv_sim_feedback (gains, feedforward, integrator state, clamp)."""
+
+    _fields_ = [("gain", ctypes.c_void_p), ("integral_gain", ctypes.c_void_p), ("gain_batch", ctypes.c_int64),
+                ("feedforward", ctypes.c_void_p), ("z_in", ctypes.c_void_p), ("z_out", ctypes.c_void_p),
+                ("clip_lo", ctypes.c_double), ("clip_hi", ctypes.c_double)]
+
+
 # the C types of the header's structures (tests/test_native_binding.py compares sizes and field offsets with the host compiler's)
 STRUCTS = {Param: "excenv_param_t", PmsmLut: "excenv_pmsm_lut_t", Props: "excenv_props_t", LaunchOpts: "excenv_launch_opts_t",
-           TrajGym: "excenv_traj_gym_t", Control: "excenv_control_t"}
+           TrajGym: "excenv_traj_gym_t", Control: "excenv_control_t", Feedback: "excenv_feedback_t"}
 
 _vp, _ci, _i32, _i64, _cd = ctypes.c_void_p, ctypes.c_int, ctypes.c_int32, ctypes.c_int64, ctypes.c_double
 _STEP = [_ci, _ci, _ci, _i64, _vp, _vp, _cd, _vp, _vp, _vp, _vp]  # env, solver, dtype, B, props, control, tau, in, action, out, obs
@@ -127,6 +135,9 @@ PROTOTYPES = {
     "excenv_step_jacobian": (_ci, [_ci, _ci, _ci, _i64, _i64, _i32, _vp, _i32, _cd, _cd, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _ci,
                                    _vp, _vp, _vp]),
     "excenv_step_jacobian_bytes": (_i64, [_ci, _ci, _ci]),
+    # env, solver, dtype, B, K, substeps, props, control, obs_stepsize, env_tau, state_in, policy, obs_traj, state_traj, last_state,
+    # actions_out, opts, stream
+    "excenv_sim_feedback": (_ci, [_ci, _ci, _ci, _i64, _i64, _i32, _vp, _vp, _cd, _cd, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "excenv_state_from_observation": (_ci, [_ci, _ci, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "excenv_update_ref": (_ci, [_ci, _ci, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
     "excenv_observe": (_ci, [_ci, _ci, _i64, _vp, _vp, _vp, _vp, _vp]),

@@ -438,6 +438,45 @@ int excenv_step_jacobian(int env, int solver, int dtype, int64_t B, int64_t rows
                          int64_t action_env_stride, int row_kind, void* jacobian, const excenv_launch_opts_t* opts, void* stream);
 int64_t excenv_step_jacobian_bytes(int env, int dtype, int row_kind);
 
+/* ---- closed-loop trajectories: excenv_sim_ahead under EXCENV_SEM_STEP with every action row computed INSIDE the one persistent
+ * launch of sim_feedback_kernel, from the observation row saved at the action's start (an addition, same ABI version: a binder
+ * probes for the symbol). Affine output feedback with optional integral action and a feedforward row. With N = K * substeps,
+ * OW = O + n_control and obs_n the saved observation row n (reference columns included), at every action row k, n = k * substeps,
+ * per environment and action component q:
+ *   acc = ff[k][q] (0 without feedforward);  acc = acc + z[q] (with integral action only)
+ *   acc = fma(gain[q][o], obs_n[o], acc) for o = 0 .. OW-1, in this order;  a[k][q] = min(max(acc, clip_lo), clip_hi)
+ *   zi = 0;  zi = fma(integral_gain[q][o], obs_n[o], zi) for o = 0 .. OW-1
+ *   z[q] = min(max(z[q] + action_stepsize * zi, clip_lo), clip_hi)            (action_stepsize = obs_stepsize * substeps)
+ * and the normalised action a[k] is held for `substeps` steps of excenv_step's arithmetic (PMSM: hexagon constraint and dead-time
+ * buffer included, substeps == 1). A NaN passes through both clamps; the integrator's clamp is the anti-windup.
+ *   gain, integral_gain : lane-major [A][OW][gain_batch], gain_batch 1 (one gain set for every environment) or B (one per
+ *                         environment); read once per launch
+ *   feedforward         : lane-major [K][A][B] or NULL
+ *   z_in, z_out         : the integrator state [A][B] before (NULL: zeros) and after the trajectory; both only touched with
+ *                         integral_gain, which requires z_out. They may be the same array.
+ *   obs_traj            : (out) [N+1][OW][B];  state_traj: (out) S pointers to [N+1][B], or NULL;  last_state: (out) S pointers to [B]
+ *   actions_out         : (out) the applied normalised actions [K][A][B], or NULL
+ * Rows are the post-processed states excenv_step carries: obs_traj / state_traj / last_state are bit for bit what excenv_sim_ahead
+ * returns under EXCENV_SEM_STEP for `actions_out`. Properties may be per-environment arrays; pmsm_lut selects the saturated model
+ * (tables read from global memory). Never allocates or synchronises. K == 0: row 0 only; B == 0: EXCENV_OK without a launch.
+ * excenv_last_launch() reports "sim_feedback_kernel". EXCENV_ENULL names a missing pointer (policy, policy->gain, obs_traj,
+ * last_state, z_out with integral_gain, ...). EXCENV_EINVAL: gain_batch other than 1 or B, clip_lo > clip_hi or a NaN bound, PMSM
+ * with substeps != 1, opts->envs_per_lane other than 0 or 1 (one environment per lane is the only form). */
+typedef struct {
+  const void* gain;          /* [A][OW][gain_batch], required */
+  const void* integral_gain; /* [A][OW][gain_batch] or NULL */
+  int64_t gain_batch;        /* 1 or B */
+  const void* feedforward;   /* [K][A][B] or NULL */
+  const void* z_in;          /* [A][B] or NULL (zeros); read only with integral_gain */
+  void* z_out;               /* [A][B]; required with integral_gain */
+  double clip_lo;            /* -inf: no lower clamp */
+  double clip_hi;            /* +inf: no upper clamp */
+} excenv_feedback_t;
+int excenv_sim_feedback(int env, int solver, int dtype, int64_t B, int64_t K, int32_t substeps, const excenv_props_t* props,
+                        const excenv_control_t* control, double obs_stepsize, double env_tau, const void* const* state_in,
+                        const excenv_feedback_t* policy, void* obs_traj, void* const* state_traj, void* const* last_state,
+                        void* actions_out, const excenv_launch_opts_t* opts, void* stream);
+
 /* ---- replaces CoreEnvironment.vmap_generate_state_from_observation (core_env.py:689-705; per env e.g.
  * pendulum_env.py:331-364, pmsm_env.py:921-970): obs [B][O + n_control] row-major -> denormalised physical state leaves
  * state_out[S][B] and, for each controlled field control_idx[j], its denormalised reference leaf reference_out[j][B]
