@@ -243,17 +243,24 @@ __device__ __forceinline__ double cos_t(double x) { return ::cos(x); }
 
 // ---- fp64 sin / cos for the reverse-mode kernels (kernels_vjp.hpp) ---------------------------------------------------------------
 // The device library's fp64 sincos carries its full-range (Payne-Hanek) path inline: some hundred registers and a few KB per call
-// site, and an RK adjoint in fp64 has up to 36 of them. The reverse pass evaluates Jacobians at saved (wrapped) angles and stage
-// states next to them, so a two-constant Cody-Waite reduction by pi/2 (fdlibm's pio2_1 / pio2_1t; n * pio2_1 is exact for
-// |n| < 2^20, i.e. |x| < 1.6e6) and fdlibm's kernel polynomials do: absolute error <= 2e-16 in that range — a Jacobian moved by
-// rounding only. Straight-line on purpose (no range test, no call): beyond that range the reduction loses accuracy gradually
-// (the only unwrapped angle the reverse pass can meet is a caller's own initial angle in row 0 under the step semantics); NaN and
-// inf give NaN. The forward kernels keep the library's routine (their bits are pinned against the oracle).
+// site, and an RK adjoint in fp64 has up to 36 of them. The reverse pass evaluates Jacobians at saved angles and stage states
+// next to them, so a two-constant Cody-Waite reduction by pi/2 (fdlibm's pio2_1 / pio2_1t; each fma rounds once, and its result
+// is small next to x) and fdlibm's kernel polynomials do. Straight-line on purpose (no range test, no call). The angles are
+// whatever the caller carries: "ahead" rows are never wrapped, row 0 of the step semantics is the caller's own. Absolute error
+// against sinl / cosl, tools/sincos_lean_restate.c on the CPU (2e6 points per decade and the neighbours of multiples of pi/2)
+// and test_device_sincos_lean_* on the GPU:
+//   |x| <= 1e10: <= 2e-16 (measured 1.3e-16) — a Jacobian moved by rounding only;
+//   |x| <= 1e12: <= 4e-15 (measured 2.3e-15); beyond, the error grows in proportion to |x| (half an ulp of n * pio2_1t:
+//   2.2e-12 at 1e15), with no jump: the first remainder x - n * pio2_1 has magnitude 3.9e-11 |x| and is rounded once.
+// The quadrant n mod 4 is taken in floating point (n / 4, floor and the fma are exact for every finite n), so no finite angle
+// can give a wrong quadrant; it used to be (int)n, out of range from |x| = 2^31 * pi/2 = 3.37e9 on, where sin and cos came out
+// with the wrong sign or swapped. NaN and inf give NaN. The forward kernels keep the library's routine (their bits are pinned
+// against the oracle).
 __device__ __forceinline__ void sincos_lean(double x, double& s, double& c) {
   const double n = __builtin_rint(x * 6.36619772367581382433e-01);  // x * 2/pi
   double r = xfma(-n, 1.57079632673412561417e+00, x);
   r = xfma(-n, 6.07710050650619224932e-11, r);
-  const int q = (int)n;
+  const int q = (int)xfma(-4.0, __builtin_floor(n * 0.25), n);  // 0 .. 3 (NaN: r is NaN already)
   const double z = r * r;
   double ps = xfma(1.58969099521155010221e-10, z, -2.50507602534068634195e-08);
   ps = xfma(ps, z, 2.75573137070700676789e-06);

@@ -812,7 +812,8 @@ int excenv_allgather(void* nccl_comm, int dtype, const void* send, void* recv, i
 }
 
 int excenv_probe_math(int which, int dtype, int64_t n, const void* in, void* out, void* stream) {
-  if (which < 0 || which > 2 || n < 0 || (dtype != EXCENV_F32 && dtype != EXCENV_F64)) { set_error("excenv_probe_math: bad argument"); return EXCENV_EINVAL; }
+  if (which < 0 || which > 4 || n < 0 || (dtype != EXCENV_F32 && dtype != EXCENV_F64)) { set_error("excenv_probe_math: bad argument"); return EXCENV_EINVAL; }
+  if (which > 2 && dtype != EXCENV_F64) { set_error("excenv_probe_math: which = 3 / 4 (sincos_lean) exist in fp64 only"); return EXCENV_EINVAL; }
   if (!in || !out) { set_error("excenv_probe_math: NULL argument"); return EXCENV_ENULL; }
   if (n == 0) return EXCENV_OK;
   const dim3 grid((unsigned)((n + 255) / 256)), block(256);

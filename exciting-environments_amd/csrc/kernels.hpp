@@ -710,7 +710,15 @@ template <typename T> __global__ void probe_kernel(int which, int64_t n, const T
   T r;
   if (which == 0) r = sin_t(x);
   else if (which == 1) r = cos_t(x);
-  else r = wrap_angle(x);
+  else if (which == 2) r = wrap_angle(x);
+  else {  // 3 sin, 4 cos through the reverse-mode kernels' routine (fp64 only: the host refuses fp32)
+    r = x;
+    if constexpr (sizeof(T) == 8) {
+      double s, c;
+      sincos_lean(x, s, c);
+      r = (which == 3) ? s : c;
+    }
+  }
   out[i] = r;
 }
 

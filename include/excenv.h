@@ -544,8 +544,10 @@ int excenv_stream_pattern(int32_t n_read, const void* const* read_base, const in
                           int32_t n_write, void* const* write_base, const int64_t* write_row_stride_bytes,
                           int64_t row_bytes, int64_t rows, int32_t nontemporal, void* stream);
 
-/* ---- device-math probes (tests only): out[i] = f(in[i]) for the in-kernel fp32 routines -- */
-int excenv_probe_math(int which /*0 sin,1 cos,2 wrap_angle*/, int dtype, int64_t n,
+/* ---- device-math probes (tests only): out[i] = f(in[i]) for the in-kernel routines. 0 / 1 / 2 in either dtype (the forward
+ * kernels' sin, cos and wrap_angle); 3 / 4 are sin and cos through the reverse-mode kernels' fp64 routine (devmath.hpp
+ * sincos_lean): EXCENV_F64 only, EXCENV_EINVAL otherwise. -- */
+int excenv_probe_math(int which /*0 sin,1 cos,2 wrap_angle,3 lean sin,4 lean cos*/, int dtype, int64_t n,
                       const void* in, void* out, void* stream);
 
 /* out_fast[i] = the kernels' division by a loop-invariant denominator (devmath.hpp InvDiv) of num[i] by den[i];

@@ -626,6 +626,154 @@ def test_device_wrap_angle_is_python_modulo_bit_exact():
             assert np.isnan(_native.probe_math(2, torch.tensor([bad], dtype=dt).cuda()).item())
 
 
+HALF_PI_LD = np.longdouble("1.57079632679489661923132169163975144")
+# |x| up to which devmath.hpp documents sincos_lean, with the bound of each range (the header's figures)
+LEAN_RANGES = ((1.6e6, 2e-16), (1e10, 2e-16), (1e12, 4e-15))
+
+
+def _trig_error(fn, x, got, subsample=4000):
+    """|got - sin / cos(x)| for float64 points against extended precision: np.longdouble where it carries more than 60 bits (x87),
+    else mpmath on a subsample, the subtraction inside mpmath so that the reference is never rounded to a double (which alone would
+    cost half an ulp, 1.1e-16, of bounds of 2e-16) -> (error, reference rounded to float64, indices of the points covered)"""
+    if np.finfo(np.longdouble).eps < 1e-18:
+        with np.errstate(invalid="ignore"):
+            want = {"sin": np.sin, "cos": np.cos}[fn](x.astype(np.longdouble))
+        return np.abs(got.astype(np.longdouble) - want).astype(np.float64), want.astype(np.float64), np.arange(x.size)
+    import mpmath
+
+    mpmath.mp.prec = 120
+    idx = np.unique(np.concatenate([np.linspace(0, x.size - 1, subsample).astype(np.int64), np.arange(min(x.size, 64))]))
+    f = {"sin": mpmath.sin, "cos": mpmath.cos}[fn]
+    err, want = np.full(idx.size, np.nan), np.full(idx.size, np.nan)
+    for i, (v, g) in enumerate(zip(x[idx], got[idx])):
+        if np.isfinite(v) and np.isfinite(g):
+            ref = f(mpmath.mpf(float(v)))
+            err[i], want[i] = float(abs(mpmath.mpf(float(g)) - ref)), float(ref)
+    return err, want, idx
+
+
+def _lean_points(limit, n=200_000, seed=11):
+    """Both signs: log-spaced magnitudes up to `limit`, and multiples of pi/2 up to it with both neighbours"""
+    rng = np.random.default_rng(seed)
+    mag = np.exp(rng.uniform(np.log(1e-3), np.log(limit), n))
+    k = np.round(np.exp(rng.uniform(0.0, np.log(limit / (np.pi / 2)), n // 4))).astype(np.longdouble)
+    near = (k * HALF_PI_LD).astype(np.float64)
+    near = near[near <= limit]
+    x = np.concatenate([mag, near, np.nextafter(near, np.inf), np.nextafter(near, -np.inf), [limit]])
+    return np.concatenate([x, -x])
+
+
+def test_device_sincos_lean_fp64_within_its_documented_error():
+    """devmath.hpp sincos_lean, the fp64 sin / cos of the four differentiable kernels (probe 3 / 4), against extended precision:
+    absolute error <= 2e-16 on wrapped angles, a few turns, the neighbours of k pi/2 for |k| <= 40 000 and every magnitude up to
+    1.6e6 (the source's first claim; tools/sincos_lean_restate.c measures 1.2e-16 on the CPU), and the header's bounds beyond:
+    <= 2e-16 up to 1e10, <= 4e-15 up to 1e12. The angle of a caller is not wrapped ("ahead" rows, row 0 under "step"): with the
+    quadrant taken from (int)n the last two ranges gave errors of 2.0 from |x| = 2^31 pi/2 = 3.37e9 on. NaN and inf give NaN;
+    the routine exists in fp64 only."""
+    from exciting_environments_amd import _native
+
+    k = (np.arange(-40000, 40001).astype(np.longdouble) * HALF_PI_LD).astype(np.float64)
+    dense = np.concatenate([np.linspace(-np.pi, np.pi, 2_000_001), np.linspace(-50.0, 50.0, 500_001), k, np.nextafter(k, np.inf),
+                            np.nextafter(k, -np.inf), [0.0, -0.0, 1e-300, -1e-200]])
+    sets = [("wrapped, +-50 and k pi/2", dense, 2e-16)]
+    sets += [(f"|x| <= {limit:g}", _lean_points(limit), bound) for limit, bound in LEAN_RANGES]
+    for name, x, bound in sets:
+        xd = torch.as_tensor(x, dtype=torch.float64).cuda()
+        for which, fn in ((3, "sin"), (4, "cos")):
+            got = _native.probe_math(which, xd).cpu().numpy()
+            err = float(_trig_error(fn, x, got)[0].max())
+            print(f"sincos_lean {fn} {name}: {x.size} points, worst absolute error {err:.3e}, bound {bound:.1e}")
+            assert np.isfinite(got).all() and err <= bound, (name, fn, err)
+    bad = torch.tensor([np.nan, np.inf, -np.inf], dtype=torch.float64).cuda()
+    for which in (3, 4):
+        assert bool(torch.isnan(_native.probe_math(which, bad)).all())
+        zero = _native.probe_math(which, torch.tensor([0.0, -0.0], dtype=torch.float64).cuda()).cpu().numpy()
+        assert np.array_equal(zero, [0.0, 0.0] if which == 3 else [1.0, 1.0])
+        with pytest.raises(RuntimeError):
+            _native.probe_math(which, torch.zeros(4, dtype=torch.float32).cuda())
+
+
+def test_device_sincos_fp64_within_2ulp():
+    """The forward kernels' fp64 sin / cos (devmath.hpp sin_t / cos_t in fp64: the device library) on wrapped angles and a few
+    turns: <= 2 ulp, or <= 4e-25 absolute next to a zero."""
+    from exciting_environments_amd import _native
+
+    k = (np.arange(-32, 33).astype(np.longdouble) * HALF_PI_LD).astype(np.float64)
+    x = np.concatenate([np.linspace(-np.pi, np.pi, 2_000_001), np.linspace(-50.0, 50.0, 500_001), k, np.nextafter(k, np.inf),
+                        np.nextafter(k, -np.inf), [0.0, -0.0, 1e-300, -1e-200, np.pi, -np.pi, np.pi / 2]])
+    xd = torch.as_tensor(x, dtype=torch.float64).cuda()
+    for which, fn in ((0, "sin"), (1, "cos")):
+        got = _native.probe_math(which, xd).cpu().numpy()
+        diff, want, idx = _trig_error(fn, x, got)
+        ulp = np.maximum(np.spacing(np.abs(want)), 2.0 ** -1074)
+        ok = (diff <= 2.0 * ulp) | (diff <= 4e-25)
+        print(f"fp64 {fn}: {x.size} points, worst {float((diff / ulp).max()):.3f} ulp")
+        assert ok.all(), (fn, float((diff / ulp)[~ok].max()))
+
+
+@pytest.mark.parametrize("dt,npdt", [(torch.float32, np.float32), (torch.float64, np.float64)], ids=["float32", "float64"])
+def test_device_wrap_angle_at_the_turn_boundaries_and_in_mixed_waves(dt, npdt):
+    """pymod_two_pi estimates the truncated quotient with a reciprocal multiply, off by at most one: the places where it is off are
+    the neighbours of 2 pi k. theta = 2 pi k and 2 pi k - pi (so that theta + pi is next to a multiple) with their +-1 and +-2 ulp
+    neighbours, k over the powers of two and random k up to 2^22, both signs; then a mixed wave: one value past the guard
+    (|theta| >= 2.64e7: the library's remainder loop) per 64 at lane 0, 31 or 63 among ordinary angles. np.remainder is the
+    reference, bit for bit."""
+    from exciting_environments_amd import _native
+    from helpers_cold import MOD_LIMIT
+
+    rng = np.random.default_rng(6)
+    pi, two_pi = npdt(np.pi), npdt(2 * np.pi)
+    k = np.concatenate([2.0 ** np.arange(0, 23), rng.integers(1, 1 << 22, 200_000).astype(np.float64)]).astype(npdt)
+    base = np.concatenate([k * two_pi, k * two_pi - pi])
+    base = np.concatenate([base, -base])
+    pts = [base]
+    for direction in (np.inf, -np.inf):
+        one = np.nextafter(base, npdt(direction))
+        pts += [one, np.nextafter(one, npdt(direction))]
+    x = np.concatenate(pts).astype(npdt)
+    want = np.remainder(x + pi, two_pi) - pi
+    got = _native.probe_math(2, torch.as_tensor(x).cuda()).cpu().numpy()
+    assert got.dtype == want.dtype
+    print(f"wrap_angle {npdt.__name__}: {x.size} points next to 2 pi k, {int((got != want).sum())} differ")
+    assert np.array_equal(got, want), int((got != want).sum())
+    # mixed waves
+    x = rng.uniform(-10, 10, 64 * 300).astype(npdt)
+    for w in range(300):
+        x[64 * w + (0, 31, 63)[w % 3]] = npdt((-1) ** w * rng.uniform(1.01 * MOD_LIMIT, 1e9))
+    assert (np.abs(x) >= MOD_LIMIT).sum() == 300
+    want = np.remainder(x + pi, two_pi) - pi
+    got = _native.probe_math(2, torch.as_tensor(x).cuda()).cpu().numpy()
+    assert np.array_equal(got, want), int((got != want).sum())
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
+def test_invariant_division_in_a_mixed_wave(dtype):
+    """InvDiv::div's guard is a wave-wide ballot and the plain division is then selected per lane: one quotient per 64 outside
+    the window (a zero numerator, 2^70 / 2^-70 in fp32 or 2^500 / 2^-500 in fp64, NaN) at lane 0, 31 or 63, the rest inside.
+    Every lane has the bits of the plain division."""
+    from exciting_environments_amd import _native
+
+    g = torch.Generator(device="cuda")
+    g.manual_seed(78)
+    n = 64 * 3000
+    it = torch.int32 if dtype == torch.float32 else torch.int64
+    big = 70 if dtype == torch.float32 else 500
+    num = torch.ldexp(torch.rand(n, generator=g, dtype=dtype, device="cuda") + 1.0, torch.randint(-20, 21, (n,), generator=g, device="cuda"))
+    den = torch.ldexp(torch.rand(n, generator=g, dtype=dtype, device="cuda") + 1.0, torch.randint(-20, 21, (n,), generator=g, device="cuda"))
+    num = num * (torch.randint(0, 2, (n,), generator=g, device="cuda").to(dtype) * 2 - 1)
+    w = torch.arange(n // 64, device="cuda")
+    at = 64 * w + torch.tensor([0, 31, 63], device="cuda")[w % 3]
+    kind = (w // 3) % 3
+    num[at] = torch.where(kind == 0, torch.zeros((), dtype=dtype, device="cuda"),
+                          torch.where(kind == 1, torch.full((), 2.0 ** big, dtype=dtype, device="cuda"),
+                                      torch.full((), float("nan"), dtype=dtype, device="cuda")))
+    den[at] = torch.where(kind == 1, torch.full((), 2.0 ** -big, dtype=dtype, device="cuda"), den[at])
+    fast, ref = _native.probe_div(num, den)
+    same = (fast.view(it) == ref.view(it)) | (torch.isnan(fast) & torch.isnan(ref))
+    assert bool(same.all()), (num[~same][:4], den[~same][:4], fast[~same][:4], ref[~same][:4])
+    assert bool(torch.isnan(ref[at][kind == 2]).all()) and bool((ref[at][kind == 0] == 0).all())
+
+
 @pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
 def test_invariant_division_has_the_bits_of_plain_division(dtype):
     """devmath.hpp InvDiv (division by a loop-invariant denominator: precomputed refined reciprocal + the compiler's own
