@@ -35,8 +35,8 @@ __device__ __forceinline__ __attribute__((nodebug)) double xsqrt(double a) { ret
 __device__ __forceinline__ bool sqrt_exceeds_one(float s) { return s > 1.00000011920928955078125f; }   // 1 + 2^-23
 __device__ __forceinline__ bool sqrt_exceeds_one(double s) { return s > 1.0000000000000002220446049250313; }  // 1 + 2^-52
 // (the library's bit-serial remainder loop: out of line, see sincos_lib below — taken only for |x| / 2 pi >= 2^22, NaN, inf)
-__device__ __attribute__((noinline)) float xfmod_slow(float a, float b) { return fmodf(a, b); }
-__device__ __attribute__((noinline)) double xfmod_slow(double a, double b) { return fmod(a, b); }
+static __device__ __attribute__((noinline)) float xfmod_slow(float a, float b) { return fmodf(a, b); }
+static __device__ __attribute__((noinline)) double xfmod_slow(double a, double b) { return fmod(a, b); }
 
 // jnp.maximum / jnp.minimum against a bound: NaN in x propagates (jnp.clip semantics).
 template <typename T> __device__ __forceinline__ __attribute__((nodebug)) T max_nan(T x, T lo) { return (x < lo) ? lo : x; }
@@ -198,7 +198,7 @@ __device__ __forceinline__ void sincos_fast(float x, float& s, float& c);
 // code object instead of once per call site. Inlined, every sincos_t of a trajectory loop carried its own copy — the lean gym
 // loops of cart-pole / acrobot (20 call sites per half loop) were 80 KB, 130 KB after the guards became wave-uniform; with the
 // call they are 44 KB, register counts unchanged, no scratch (round 5, tools/loop_code_size.py). Never executed for |x| <= 65536.
-__device__ __attribute__((noinline)) float2 sincos_lib(float x) { return make_float2(::sinf(x), ::cosf(x)); }
+static __device__ __attribute__((noinline)) float2 sincos_lib(float x) { return make_float2(::sinf(x), ::cosf(x)); }
 __device__ __forceinline__ void sincos_t(float x, float& s, float& c) {
   sincos_fast(x, s, c);
   const bool big = !(xabs(x) <= 65536.0f);  // also NaN / inf

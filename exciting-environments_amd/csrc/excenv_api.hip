@@ -691,6 +691,57 @@ int excenv_sim_feedback(int env, int solver, int dtype, int64_t B, int64_t K, in
   return t->sim_feedback(fc);
 }
 
+int64_t excenv_sim_feedback_vjp_workspace_bytes(int env, int dtype, int64_t B, int64_t K, int32_t n_control, int64_t gain_batch,
+                                                int integral) {
+  const EnvVTable* t = table_public(env);
+  if (!t || (dtype != EXCENV_F32 && dtype != EXCENV_F64) || B < 0 || K < 0 || n_control < 0 || n_control > EXCENV_MAX_CONTROL) return -1;
+  if (gain_batch != 1 && gain_batch != B) return -1;
+  return feedback_vjp_workspace_bytes(t->A, t->O + n_control, dtype == EXCENV_F64 ? 8 : 4, B, K, gain_batch, integral != 0);
+}
+
+int64_t excenv_sim_feedback_vjp_bytes(int env, int dtype, int32_t n_control, int32_t substeps, int integral, int has_grad_obs,
+                                      int has_grad_states, int has_grad_actions) {
+  const EnvVTable* t = table_public(env);
+  if (!t || (dtype != EXCENV_F32 && dtype != EXCENV_F64) || n_control < 0 || n_control > EXCENV_MAX_CONTROL || substeps < 1) return -1;
+  return feedback_vjp_bytes(t->S, t->A, t->O, dtype == EXCENV_F64 ? 8 : 4, n_control, substeps, integral != 0, has_grad_obs != 0,
+                            has_grad_states != 0, has_grad_actions != 0);
+}
+
+int excenv_sim_feedback_vjp(int env, int solver, int dtype, int64_t B, int64_t K, int32_t substeps, const excenv_props_t* props,
+                            const excenv_control_t* control, double obs_stepsize, double env_tau,
+                            const excenv_feedback_vjp_t* call, void* workspace, int64_t workspace_bytes,
+                            const excenv_launch_opts_t* opts, void* stream) {
+  const char* fn = "excenv_sim_feedback_vjp";
+  if (int rc = check_common(fn, env, solver, dtype, B)) return rc;
+  if (K < 0 || substeps < 1) { set_error("%s: bad K=%lld or substeps=%d", fn, (long long)K, substeps); return EXCENV_EINVAL; }
+  if (int rc = check_reverse_props(fn, props)) return rc;
+  {
+    char why[256];
+    if (int rc = feedback_vjp_refusal(call, B, K, why, sizeof(why))) { set_error("%s", why); return rc; }
+  }
+  if (int rc = check_control(fn, env, control)) return rc;
+  if (int rc = check_opts(fn, opts)) return rc;
+  if (opts->envs_per_lane > 1) {
+    set_error("%s: opts.envs_per_lane = %d is not available (this kernel has the one-environment-per-lane form only)", fn, opts->envs_per_lane);
+    return EXCENV_EINVAL;
+  }
+  if (env == EXCENV_PMSM && substeps != 1) {
+    set_error("%s: PMSM: obs_stepsize must equal action_stepsize (substeps = %d; reference pmsm_env.py:787)", fn, substeps);
+    return EXCENV_EINVAL;
+  }
+  if (int rc = check_broadcast_props(fn, env, props)) return rc;
+  const EnvVTable* t = table_public(env);
+  const int64_t need = feedback_vjp_workspace_bytes(t->A, t->O + (control ? control->n_control : 0), dtype == EXCENV_F64 ? 8 : 4, B, K,
+                                                    call->gain_batch, call->integral_gain != nullptr);
+  if (B > 0 && need > 0 && (!workspace || workspace_bytes < need)) {
+    set_error("%s: workspace too small: %lld bytes needed (excenv_sim_feedback_vjp_workspace_bytes), %lld given", fn, (long long)need,
+              (long long)(workspace ? workspace_bytes : 0));
+    return EXCENV_EINVAL;
+  }
+  const FeedbackVjpCall fc{solver, dtype, B, K, substeps, props, control, obs_stepsize, env_tau, call, workspace, stream};
+  return t->sim_feedback_vjp(fc);
+}
+
 int excenv_state_from_observation(int env, int dtype, int64_t B, const excenv_props_t* props, int32_t n_control,
                                   const int32_t* control_idx, const void* obs, void* const* state_out,
                                   void* const* reference_out, void* stream) {

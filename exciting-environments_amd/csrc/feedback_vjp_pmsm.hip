@@ -1,0 +1,4 @@
+// Closed-loop reverse-mode kernel instantiations for one environment (its own translation unit so the six compile in parallel).
+#include "kernels_feedback_vjp.hpp"
+template int excenv::feedback_vjp_entry<excenv::Pmsm>(const excenv::FeedbackVjpCall&);
+template int excenv::feedback_vjp_entry<excenv::PmsmSat>(const excenv::FeedbackVjpCall&);  // the refusal: no kernel

@@ -7,6 +7,7 @@
 #include <type_traits>
 #include "kernels_emr.hpp"
 #include "feedback.hpp"
+#include "feedback_vjp.hpp"
 #include "refgen.hpp"
 #include "rew_vjp.hpp"
 #include "step_jac.hpp"
@@ -141,17 +142,19 @@ struct EnvVTable {
   int (*step_vjp)(const StepVjpCall&);  // reverse mode of step (kernels_step_vjp.hpp)
   int (*step_jac)(const StepJacCall&);  // Jacobians of step, row by row (kernels_step_jac.hpp)
   int (*sim_feedback)(const FeedbackCall&);  // sim with the actions computed in the launch (kernels_feedback.hpp)
+  int (*sim_feedback_vjp)(const FeedbackVjpCall&);  // reverse mode of sim_feedback (kernels_feedback_vjp.hpp)
 };
 
 // The reverse-mode entries of a model and its closed-loop entry: declared here so that they sit in the same table as every other entry
 // point, each defined next to its launcher (kernels_vjp.hpp, kernels_rew_vjp.hpp, kernels_step_vjp.hpp, kernels_step_jac.hpp,
-// kernels_feedback.hpp) and instantiated in the translation units that hold its kernels: vjp_<model>.hip, rew_vjp.hip,
-// step_vjp_<model>.hip, step_jac_<model>.hip, feedback_<model>.hip
+// kernels_feedback.hpp, kernels_feedback_vjp.hpp) and instantiated in the translation units that hold its kernels: vjp_<model>.hip,
+// rew_vjp.hip, step_vjp_<model>.hip, step_jac_<model>.hip, feedback_<model>.hip, feedback_vjp_<model>.hip
 template <template <typename> class MT> int vjp_entry(const VjpCall&);
 template <template <typename> class MT> int rew_vjp_entry(const RewVjpCall&);
 template <template <typename> class MT> int step_vjp_entry(const StepVjpCall&);
 template <template <typename> class MT> int step_jac_entry(const StepJacCall&);
 template <template <typename> class MT> int feedback_entry(const FeedbackCall&);
+template <template <typename> class MT> int feedback_vjp_entry(const FeedbackVjpCall&);
 
 // The one choice of the element type: launcher<MT<float>, float>(call) or launcher<MT<double>, double>(call) by the call's dtype
 #define EXCENV_BY_DTYPE(launcher, MT, call) \
@@ -706,7 +709,7 @@ template <template <typename> class MT> struct EnvEntry {
   static EnvVTable vtable() {
     return EnvVTable{MT<float>::S, MT<float>::A, MT<float>::O, MT<float>::P, &step, &sim, &traj_gym, &from_obs, &update_ref,
                      &random_state, &observe, &vjp_entry<MT>, &rew_vjp_entry<MT>, &step_vjp_entry<MT>, &step_jac_entry<MT>,
-                     &feedback_entry<MT>};
+                     &feedback_entry<MT>, &feedback_vjp_entry<MT>};
   }
 };
 

@@ -5,7 +5,7 @@ affine output feedback, optional integral action, optional feedforward row (DESI
 
 The rows are the post-processed states `vmap_step` carries ("step" semantics), so the returned observations, states and last state are
 bit for bit what `vmap_sim_ahead` returns under `sim_ahead_semantics = "step"` for the returned actions. Nothing here records a graph:
-there is no reverse mode through the policy."""
+the reverse mode through the policy is _feedback_vjp.py's, asked for with `differentiable=True`."""
 from __future__ import annotations
 
 import ctypes
@@ -37,7 +37,7 @@ class FeedbackMixin:
         return gain, B
 
     def vmap_sim_ahead_feedback(self, init_state, gain, n_actions, obs_stepsize, action_stepsize, feedforward=None,
-                                integral_gain=None, integrator_state=None, clip=(-1.0, 1.0)):
+                                integral_gain=None, integrator_state=None, clip=(-1.0, 1.0), differentiable=None):
         """Closed-loop trajectories of all batch_size environments in one kernel launch -> (observations [B, N+1, OW],
         states with leaves [B, N+1], last_state with leaves [B], actions [B, K, A], z [B, A] or None), K = n_actions action rows
         of substeps = action_stepsize / obs_stepsize solver steps each, N = K * substeps.
@@ -57,7 +57,15 @@ class FeedbackMixin:
         The returned tensors are views of freshly allocated lane-major memory; `states` is None with
         `env.store_state_trajectory = False`. `vmap_generate_rew_trunc_term_ahead(states, actions)` gives the gym outputs.
         Refused by name (ValueError): trajectory layouts other than "lane_major", `sim_ahead_semantics ==
-        "ahead_accumulated_t"`, and `env.differentiable` with an input that requires grad: the outputs carry no graph."""
+        "ahead_accumulated_t"`, and (differentiable=None, the default) `env.differentiable` with an input that requires grad: the
+        outputs carry no graph.
+
+        differentiable=True: when grad mode is on and the gain, the integral gain, the feedforward, the integrator state or a leaf
+        of the initial physical state requires grad, the call records ONE autograd node (_feedback_vjp.py) whose backward is one
+        `vmap_sim_ahead_feedback_vjp` call; observations, state leaves, last state, actions and z carry the graph, so a loss through
+        `vmap_generate_rew_trunc_term_ahead(states, actions)` under `env.differentiable` reaches `gain.grad`. With no input that
+        requires grad the plain path runs. Refused then: `store_state_trajectory = False`, static parameters that require grad, the
+        saturated PMSM, per-environment properties, graph capture."""
         if self.traj_layout != "lane_major":
             raise ValueError(f"vmap_sim_ahead_feedback: traj_layout={self.traj_layout!r}: the closed-loop kernel writes the "
                              "'lane_major' layout only")
@@ -66,10 +74,21 @@ class FeedbackMixin:
                              "of every action, its trajectory is a chain of steps ('step' semantics) on every setting")
         tensors = [gain, integral_gain, feedforward, integrator_state]
         tensors += [getattr(init_state.physical_state, n) for n in self.STATE_FIELDS]
-        if self.differentiable and torch.is_grad_enabled() and (
-                self._param_leaves() or any(isinstance(t, torch.Tensor) and t.requires_grad for t in tensors)):
+        wants = torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in tensors)
+        if differentiable:
+            if wants or (torch.is_grad_enabled() and self._param_leaves()):
+                return self._feedback_differentiable(init_state, gain, n_actions, obs_stepsize, action_stepsize, feedforward,
+                                                     integral_gain, integrator_state, clip)
+        elif self.differentiable and torch.is_grad_enabled() and (self._param_leaves() or wants):
             raise ValueError("vmap_sim_ahead_feedback: env.differentiable with an input that requires grad: there is no reverse mode "
-                             "through the policy; detach the inputs or set env.differentiable = False")
+                             "through the policy; detach the inputs or set env.differentiable = False, or pass differentiable=True, "
+                             "which records the closed loop's own reverse mode (vmap_sim_ahead_feedback_vjp)")
+        return self._feedback_launch(init_state, gain, n_actions, obs_stepsize, action_stepsize, feedforward, integral_gain,
+                                     integrator_state, clip)
+
+    def _feedback_launch(self, init_state, gain, n_actions, obs_stepsize, action_stepsize, feedforward, integral_gain,
+                         integrator_state, clip):
+        """The one excenv_sim_feedback launch behind vmap_sim_ahead_feedback (its arguments, its return value); records no graph."""
         B, S, A, OW = self.batch_size, self.physical_state_dim, self.action_dim, self._obs_dim()
         dt, dev = self.dtype, self.device
         assert obs_stepsize <= action_stepsize, "The action stepsize should be greater or equal to the observation stepsize."

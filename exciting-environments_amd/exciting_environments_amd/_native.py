@@ -85,9 +85,23 @@ class Feedback(ctypes.Structure):
                 ("clip_lo", ctypes.c_double), ("clip_hi", ctypes.c_double)]
 
 
+class FeedbackVjp(ctypes.Structure):
+    """excenv_feedback_vjp_t: the stored forward of one excenv_sim_feedback call, the cotangents of its outputs and where the
+    gradients go (excenv_sim_feedback_vjp)."""
+
+    _fields_ = [("gain", ctypes.c_void_p), ("integral_gain", ctypes.c_void_p), ("gain_batch", ctypes.c_int64),
+                ("clip_lo", ctypes.c_double), ("clip_hi", ctypes.c_double), ("obs_traj", ctypes.c_void_p),
+                ("state_traj", ctypes.c_void_p), ("actions", ctypes.c_void_p), ("z_in", ctypes.c_void_p),
+                ("grad_obs", ctypes.c_void_p), ("grad_states", ctypes.c_void_p), ("grad_last_state", ctypes.c_void_p),
+                ("grad_actions", ctypes.c_void_p), ("grad_z", ctypes.c_void_p), ("grad_state0", ctypes.c_void_p),
+                ("grad_ff", ctypes.c_void_p), ("grad_zi", ctypes.c_void_p), ("grad_z0", ctypes.c_void_p),
+                ("grad_gain", ctypes.c_void_p), ("grad_integral_gain", ctypes.c_void_p)]
+
+
 # the C types of the header's structures (tests/test_native_binding.py compares sizes and field offsets with the host compiler's)
 STRUCTS = {Param: "excenv_param_t", PmsmLut: "excenv_pmsm_lut_t", Props: "excenv_props_t", LaunchOpts: "excenv_launch_opts_t",
-           TrajGym: "excenv_traj_gym_t", Control: "excenv_control_t", Feedback: "excenv_feedback_t"}
+           TrajGym: "excenv_traj_gym_t", Control: "excenv_control_t", Feedback: "excenv_feedback_t",
+           FeedbackVjp: "excenv_feedback_vjp_t"}
 
 _vp, _ci, _i32, _i64, _cd = ctypes.c_void_p, ctypes.c_int, ctypes.c_int32, ctypes.c_int64, ctypes.c_double
 _STEP = [_ci, _ci, _ci, _i64, _vp, _vp, _cd, _vp, _vp, _vp, _vp]  # env, solver, dtype, B, props, control, tau, in, action, out, obs
@@ -138,6 +152,10 @@ PROTOTYPES = {
     # env, solver, dtype, B, K, substeps, props, control, obs_stepsize, env_tau, state_in, policy, obs_traj, state_traj, last_state,
     # actions_out, opts, stream
     "excenv_sim_feedback": (_ci, [_ci, _ci, _ci, _i64, _i64, _i32, _vp, _vp, _cd, _cd, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "excenv_sim_feedback_vjp_workspace_bytes": (_i64, [_ci, _ci, _i64, _i64, _i32, _i64, _ci]),
+    "excenv_sim_feedback_vjp_bytes": (_i64, [_ci, _ci, _i32, _i32, _ci, _ci, _ci, _ci]),
+    # env, solver, dtype, B, K, substeps, props, control, obs_stepsize, env_tau, call, workspace, workspace_bytes, opts, stream
+    "excenv_sim_feedback_vjp": (_ci, [_ci, _ci, _ci, _i64, _i64, _i32, _vp, _vp, _cd, _cd, _vp, _vp, _i64, _vp, _vp]),
     "excenv_state_from_observation": (_ci, [_ci, _ci, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "excenv_update_ref": (_ci, [_ci, _ci, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
     "excenv_observe": (_ci, [_ci, _ci, _i64, _vp, _vp, _vp, _vp, _vp]),

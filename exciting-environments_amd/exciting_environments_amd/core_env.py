@@ -30,6 +30,7 @@ from ._placement import StepSlotPool, TrajectoryPlacement
 from ._trajectory import TrajectoryLaunchMixin
 from ._reward_vjp import RewardVjpMixin
 from ._feedback import FeedbackMixin
+from ._feedback_vjp import FeedbackVjpMixin
 from ._linearize import LinearizeMixin
 from ._step_vjp import StepVjpMixin
 from ._vjp import TrajectoryVjpMixin
@@ -47,7 +48,8 @@ def _is_scalar(x) -> bool:
     return _is_array(x) and x.ndim == 0
 
 
-class CoreEnvironment(TrajectoryLaunchMixin, TrajectoryVjpMixin, RewardVjpMixin, StepVjpMixin, LinearizeMixin, FeedbackMixin, ABC):
+class CoreEnvironment(TrajectoryLaunchMixin, TrajectoryVjpMixin, RewardVjpMixin, StepVjpMixin, LinearizeMixin, FeedbackMixin,
+                      FeedbackVjpMixin, ABC):
     """Core structure of the provided environments (reference core_env.py:15-57).
 
     The simulated systems are physical state-space models dx/dt = f(x(t), u(t)); outputs are

@@ -477,6 +477,80 @@ int excenv_sim_feedback(int env, int solver, int dtype, int64_t B, int64_t K, in
                         const excenv_feedback_t* policy, void* obs_traj, void* const* state_traj, void* const* last_state,
                         void* actions_out, const excenv_launch_opts_t* opts, void* stream);
 
+/* ---- reverse mode of excenv_sim_feedback: the vector-Jacobian product of one closed-loop trajectory with respect to the initial
+ * state, the gains, the feedforward rows and the initial integrator state, from the rows that call saved (additions, same ABI
+ * version: a binder probes for the symbols). The forward, at action row k (n = k * substeps, ob = saved observation row n with all
+ * OW = O + n_control columns, adt = obs_stepsize * substeps):
+ *   acc_k = ff[k] + z_k + Gp ob;  a_k = clamp(acc_k);  zi_k = Gi ob;  z_{k+1} = clamp(z_k + adt zi_k);
+ *   s_{n+1 .. n+substeps} = env_step(s, a_k)
+ * The reverse pass walks the rows from N down to 0 and carries sb[S] (cotangent of the carried state), zb[A] (cotangent of z_{k+1},
+ * starting from grad_z) and ab[A] (the action cotangent summed over the `substeps` steps that held a_k). Per solver step
+ * n = N-1 .. 0:
+ *   1. sb += observe^T(grad_obs[n+1]) + grad_states[n+1] at the saved row n+1 (row N also takes grad_last_state). The control columns
+ *      of grad_obs are skipped: references get no gradient.
+ *   2. the transposed step of excenv_step_vjp takes sb from row n+1 back to row n, and ab += its action gradient.
+ *   3. if n is an action row (n = k * substeps):
+ *        ab += grad_actions[k]
+ *        pre[q]  = ab[q] where clip_lo < a_k[q] < clip_hi, else 0        (the stored applied action)
+ *        zpre[q] = zb[q] where clip_lo < z_{k+1}[q] < clip_hi, else 0    (the recomputed integrator row)
+ *        grad_ff[k][q] = pre[q];  grad_zi[k][q] = adt * zpre[q]
+ *        obb[o] = sum_q Gp[q][o] pre[q] + Gi[q][o] grad_zi[k][q]  for o < O;  sb += observe^T(obb) at s_n
+ *        zb[q] = pre[q] + zpre[q];  ab = 0
+ *   4. after row 0: sb += observe^T(grad_obs[0]) + grad_states[0]; grad_state0 = sb, grad_z0 = zb.
+ * grad_gain[q][o] = sum_k pre_k[q] ob_k[o] and grad_integral_gain[q][o] = sum_k grad_zi_k[q] ob_k[o] over all OW columns (the gains
+ * on reference columns do get gradients), k ascending, per environment. A clamp has derivative 0 on and outside its bounds; a NaN
+ * compares false, so its gradient is 0. The other subgradient conventions are excenv_sim_ahead_vjp's.
+ * Launches, all on `stream`, in this order: feedback_z_rows_kernel (with integral_gain and K > 0 only: the forward's own recurrence
+ * over the saved observation rows, z_1 .. z_K into the workspace; its last row equals the forward's z_out bit for bit),
+ * sim_feedback_vjp_kernel (one environment per lane), feedback_gain_grad_kernel (one launch for the requested gain gradients) and, for
+ * gain_batch == 1, the deterministic batch sum of excenv_param_grad_sum in chunks of EXCENV_MAX_STATIC entries. No atomics.
+ *   gain, integral_gain, gain_batch, clip_lo, clip_hi : as the forward call's policy
+ *   obs_traj, state_traj, actions, z_in : what the forward wrote ([N+1][OW][B], S x [N+1][B], [K][A][B]) and was given (z_in, NULL =
+ *                         zeros: the pre-pass rebuilds the integrator rows from it). state_traj and obs_traj are required.
+ *   grad_obs            : [N+1][OW][B] or NULL;  grad_states, grad_last_state: NULL, or S pointers ([N+1][B] / [B], or NULL each)
+ *   grad_actions        : [K][A][B] or NULL (cotangent of actions_out);  grad_z: [A][B] or NULL (cotangent of z_out)
+ *   grad_state0         : (out) S pointers to [B];  grad_ff: (out) [K][A][B], required;  grad_zi: (out) [K][A][B] and grad_z0: (out)
+ *                         [A][B], both required with integral_gain
+ *   grad_gain, grad_integral_gain : (out) [A][OW][gain_batch] or NULL = not wanted
+ *   workspace           : excenv_sim_feedback_vjp_workspace_bytes(env, dtype, B, K, n_control, gain_batch, integral_gain != NULL)
+ *                         bytes of device memory, 8-byte aligned (-1 for a bad argument)
+ * Never allocates or synchronises. K == 0 handles row 0 only; B == 0 returns EXCENV_OK without a launch. excenv_last_launch() reports
+ * "sim_feedback_vjp_kernel". EXCENV_ENULL names a missing required pointer. EXCENV_EINVAL: gain_batch other than 1 or B, clip_lo >
+ * clip_hi or a NaN bound, PMSM with substeps != 1, opts->envs_per_lane other than 0 or 1, a workspace that is too small (with the
+ * size). EXCENV_EUNSUPPORTED: the saturated PMSM (pmsm_lut), per-environment property arrays.
+ * excenv_sim_feedback_vjp_bytes (host only): the algorithmic bytes per environment and action row of the whole sequence; -1 for a
+ * bad argument. */
+typedef struct {
+  const void* gain;                    /* [A][OW][gain_batch], required */
+  const void* integral_gain;           /* [A][OW][gain_batch] or NULL */
+  int64_t gain_batch;                  /* 1 or B */
+  double clip_lo;
+  double clip_hi;
+  const void* obs_traj;                /* [N+1][OW][B], required */
+  const void* const* state_traj;       /* S x [N+1][B], required */
+  const void* actions;                 /* [K][A][B]: the applied actions */
+  const void* z_in;                    /* [A][B] or NULL (zeros) */
+  const void* grad_obs;                /* [N+1][OW][B] or NULL */
+  const void* const* grad_states;      /* NULL, or S pointers ([N+1][B] or NULL each) */
+  const void* const* grad_last_state;  /* NULL, or S pointers ([B] or NULL each) */
+  const void* grad_actions;            /* [K][A][B] or NULL */
+  const void* grad_z;                  /* [A][B] or NULL */
+  void* const* grad_state0;            /* S x [B] */
+  void* grad_ff;                       /* [K][A][B] */
+  void* grad_zi;                       /* [K][A][B], with integral_gain */
+  void* grad_z0;                       /* [A][B], with integral_gain */
+  void* grad_gain;                     /* [A][OW][gain_batch] or NULL */
+  void* grad_integral_gain;            /* [A][OW][gain_batch] or NULL */
+} excenv_feedback_vjp_t;
+int64_t excenv_sim_feedback_vjp_workspace_bytes(int env, int dtype, int64_t B, int64_t K, int32_t n_control, int64_t gain_batch,
+                                                int integral);
+int64_t excenv_sim_feedback_vjp_bytes(int env, int dtype, int32_t n_control, int32_t substeps, int integral, int has_grad_obs,
+                                      int has_grad_states, int has_grad_actions);
+int excenv_sim_feedback_vjp(int env, int solver, int dtype, int64_t B, int64_t K, int32_t substeps, const excenv_props_t* props,
+                            const excenv_control_t* control, double obs_stepsize, double env_tau,
+                            const excenv_feedback_vjp_t* call, void* workspace, int64_t workspace_bytes,
+                            const excenv_launch_opts_t* opts, void* stream);
+
 /* ---- replaces CoreEnvironment.vmap_generate_state_from_observation (core_env.py:689-705; per env e.g.
  * pendulum_env.py:331-364, pmsm_env.py:921-970): obs [B][O + n_control] row-major -> denormalised physical state leaves
  * state_out[S][B] and, for each controlled field control_idx[j], its denormalised reference leaf reference_out[j][B]
