@@ -742,6 +742,40 @@ int excenv_sim_feedback_vjp(int env, int solver, int dtype, int64_t B, int64_t K
   return t->sim_feedback_vjp(fc);
 }
 
+int excenv_sim_policy(int env, int solver, int dtype, int64_t B, int64_t K, int32_t substeps, const excenv_props_t* props,
+                      const excenv_control_t* control, double obs_stepsize, double env_tau, const void* const* state_in,
+                      const excenv_policy_t* policy, void* obs_traj, void* const* state_traj, void* const* last_state,
+                      void* actions_out, const excenv_launch_opts_t* opts, void* stream) {
+  const char* fn = "excenv_sim_policy";
+  if (int rc = check_common(fn, env, solver, dtype, B)) return rc;
+  if (K < 0 || substeps < 1) { set_error("%s: bad K=%lld or substeps=%d", fn, (long long)K, substeps); return EXCENV_EINVAL; }
+  if (!props) { set_error("%s: props is NULL", fn); return EXCENV_ENULL; }
+  if (!state_in) { set_error("%s: state_in is NULL", fn); return EXCENV_ENULL; }
+  if (!obs_traj) { set_error("%s: obs_traj is NULL", fn); return EXCENV_ENULL; }
+  if (!last_state) { set_error("%s: last_state is NULL", fn); return EXCENV_ENULL; }
+  if (int rc = check_control(fn, env, control)) return rc;  // (before the policy: its first width is O + n_control)
+  {
+    char why[256];
+    const EnvVTable* d = table_public(env);
+    if (int rc = policy_refusal(policy, d->O + (control ? control->n_control : 0), d->A, why, sizeof(why))) { set_error("%s", why); return rc; }
+  }
+  if (int rc = check_opts(fn, opts)) return rc;
+  if (opts->envs_per_lane > 1) {
+    set_error("%s: opts.envs_per_lane = %d is not available (this kernel has the one-environment-per-lane form only)", fn, opts->envs_per_lane);
+    return EXCENV_EINVAL;
+  }
+  if (env == EXCENV_PMSM && substeps != 1) {
+    set_error("%s: PMSM: obs_stepsize must equal action_stepsize (substeps = %d; reference pmsm_env.py:787)", fn, substeps);
+    return EXCENV_EINVAL;
+  }
+  int trc;
+  const EnvVTable* t = table_for(env, props, &trc);
+  if (!t) return trc;
+  const PolicyCall pc{solver, dtype, B, K, substeps, props, control, obs_stepsize, env_tau, state_in, policy, obs_traj, state_traj,
+                      last_state, actions_out, stream};
+  return t->sim_policy(pc);
+}
+
 int excenv_state_from_observation(int env, int dtype, int64_t B, const excenv_props_t* props, int32_t n_control,
                                   const int32_t* control_idx, const void* obs, void* const* state_out,
                                   void* const* reference_out, void* stream) {

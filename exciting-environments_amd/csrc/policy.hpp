@@ -1,0 +1,85 @@
+// Policy rollouts: what one excenv_sim_policy call launches. Host-only and free of HIP, like feedback.hpp: the call record, what the
+// entry point refuses about the policy before any launch, the layout of the parameter array, the dynamic LDS of a launch and the
+// name of sim_policy_kernel (kernels_policy.hpp).
+#pragma once
+#include <cstdint>
+#include <cstdio>
+#include "../../include/excenv.h"
+
+namespace excenv {
+
+// The validated call (excenv_api.hip): K action rows of `substeps` solver steps each for B environments, every action computed inside
+// the launch by a small MLP on the observation row saved at its start (include/excenv.h excenv_policy_t).
+struct PolicyCall {
+  int solver, dtype;
+  int64_t B, K;
+  int32_t substeps;
+  const excenv_props_t* props;
+  const excenv_control_t* control;  // nullptr when n_control == 0
+  double obs_stepsize, env_tau;     // the solver's step and the environment's tau (PMSM's dead-time advance)
+  const void* const* state_in;      // S pointers
+  const excenv_policy_t* policy;
+  void* obs_traj;                   // [N + 1][O + n_control][B]
+  void* const* state_traj;          // S pointers to [N + 1][B], or nullptr
+  void* const* last_state;          // S pointers to [B]
+  void* actions_out;                // [K][A][B] or nullptr
+  void* stream;                     // hipStream_t
+};
+
+// sim_policy_kernel<M, T, SOLVER> exists for the seven models (the saturated PMSM included), the three solvers and both element
+// types, one environment per lane: the only form, so excenv_launch_opts_t.envs_per_lane must be 0 (auto) or 1.
+constexpr const char* policy_name() { return "sim_policy_kernel"; }
+
+// One wavefront per workgroup: the kernel has no barrier, a lane only reads the LDS column it wrote, and the widest call (two
+// ping-pong buffers of 64 fp64 activations per lane) then takes 64 KB of the CU's 160 KB, so two such workgroups still share a CU.
+constexpr int POLICY_BLOCK = 64;
+
+// The widest hidden layer of a validated policy (0 for L == 1), and the dynamic LDS of its launch: h[2][widest][POLICY_BLOCK]
+inline int policy_widest_hidden(const excenv_policy_t& p) {
+  int w = 0;
+  for (int l = 1; l < p.n_layers; ++l) w = p.widths[l] > w ? p.widths[l] : w;
+  return w;
+}
+inline size_t policy_lds_bytes(const excenv_policy_t& p, size_t elem) { return 2 * (size_t)policy_widest_hidden(p) * POLICY_BLOCK * elem; }
+
+// The number of elements of `params`: for each layer W_l [d_l][d_{l-1}], then b_l [d_l]
+inline int64_t policy_param_count(const excenv_policy_t& p) {
+  int64_t n = 0;
+  for (int l = 1; l <= p.n_layers; ++l) n += (int64_t)p.widths[l] * (p.widths[l - 1] + 1);
+  return n;
+}
+
+// What excenv_sim_policy refuses about the policy record for an environment of observation width OW and A actions: EXCENV_OK, or
+// the code with the message in `msg`. NULL pointers first, then values. A NaN bound fails `lo <= hi`.
+inline int policy_refusal(const excenv_policy_t* p, int OW, int A, char* msg, size_t n) {
+  const char* fn = "excenv_sim_policy";
+  if (!p) { std::snprintf(msg, n, "%s: policy is NULL", fn); return EXCENV_ENULL; }
+  if (!p->params) { std::snprintf(msg, n, "%s: policy->params is NULL", fn); return EXCENV_ENULL; }
+  if (p->n_layers < 1 || p->n_layers > EXCENV_POLICY_MAX_LAYERS) {
+    std::snprintf(msg, n, "%s: policy->n_layers must be 1 .. %d (got %d)", fn, EXCENV_POLICY_MAX_LAYERS, p->n_layers);
+    return EXCENV_EINVAL;
+  }
+  if (p->widths[0] != OW || p->widths[p->n_layers] != A) {
+    std::snprintf(msg, n, "%s: policy->widths must run from the observation width %d to the action width %d (got %d .. %d)", fn, OW, A,
+                  p->widths[0], p->widths[p->n_layers]);
+    return EXCENV_EINVAL;
+  }
+  for (int l = 1; l < p->n_layers; ++l) {
+    if (p->widths[l] < 1 || p->widths[l] > EXCENV_POLICY_MAX_WIDTH) {
+      std::snprintf(msg, n, "%s: policy->widths[%d] must be 1 .. %d (got %d)", fn, l, EXCENV_POLICY_MAX_WIDTH, p->widths[l]);
+      return EXCENV_EINVAL;
+    }
+  }
+  if (p->activation != EXCENV_ACT_RELU && p->activation != EXCENV_ACT_TANH) {
+    std::snprintf(msg, n, "%s: policy->activation must be EXCENV_ACT_RELU (0) or EXCENV_ACT_TANH (1) (got %d)", fn, p->activation);
+    return EXCENV_EINVAL;
+  }
+  if (!(p->clip_lo <= p->clip_hi)) {
+    std::snprintf(msg, n, "%s: policy->clip_lo = %g and policy->clip_hi = %g are not an interval (-inf / +inf: no clamp)", fn, p->clip_lo,
+                  p->clip_hi);
+    return EXCENV_EINVAL;
+  }
+  return EXCENV_OK;
+}
+
+}  // namespace excenv

@@ -1,0 +1,4 @@
+// Policy rollout kernel instantiations for one environment (its own translation unit so the six compile in parallel).
+#include "kernels_policy.hpp"
+template int excenv::policy_entry<excenv::Pmsm>(const excenv::PolicyCall&);
+template int excenv::policy_entry<excenv::PmsmSat>(const excenv::PolicyCall&);  // the saturated model: tables in global memory

@@ -13,6 +13,7 @@ from .core_env import CoreEnvironment
 from .envs import Acrobot, CartPole, FluidTank, MassSpringDamper, MotorVariant, Pendulum, PMSM, load_pmsm_lut, prepare_pmsm_lut
 from .registration import EnvironmentRegistry
 from .gym_wrapper import GymWrapper
+from ._policy import MLPPolicy
 from .solvers import Euler, RK4, Tsit5
 from .stepper import Stepper
 from .utils import MinMaxNormalization, dump_sim_properties_to_json, load_sim_properties_from_json
@@ -20,6 +21,6 @@ from . import random, tree, utils
 
 __all__ = [
     "CoreEnvironment", "Acrobot", "CartPole", "FluidTank", "MassSpringDamper", "Pendulum", "PMSM", "MotorVariant", "prepare_pmsm_lut", "load_pmsm_lut",
-    "EnvironmentRegistry", "GymWrapper", "Stepper", "Euler", "RK4", "Tsit5", "MinMaxNormalization", "dump_sim_properties_to_json",
+    "EnvironmentRegistry", "GymWrapper", "MLPPolicy", "Stepper", "Euler", "RK4", "Tsit5", "MinMaxNormalization", "dump_sim_properties_to_json",
     "load_sim_properties_from_json", "random", "tree", "utils",
 ]

@@ -30,6 +30,9 @@ JAC_ROWS = {"state": JAC_STATE, "obs": JAC_OBS}
 OPT_NO_FUSED_ACTIONS = 1  # EXCENV_OPT_NO_FUSED_ACTIONS
 OPT_KEEP_CONSTANT_COLUMNS = 2  # EXCENV_OPT_KEEP_CONSTANT_COLUMNS
 ABI_VERSION = 7
+POLICY_MAX_LAYERS, POLICY_MAX_WIDTH = 4, 64  # excenv_policy_t: linear layers of the MLP, units of a hidden layer
+ACT_RELU, ACT_TANH = 0, 1
+ACTIVATIONS = {"relu": ACT_RELU, "tanh": ACT_TANH}
 
 _LIB_PATH = os.environ.get(  # EXCENV_HIP_LIB: A/B-test another build of the same library (tuning experiments)
     "EXCENV_HIP_LIB", os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libexcenv_hip.so"))
@@ -98,10 +101,18 @@ class FeedbackVjp(ctypes.Structure):
                 ("grad_gain", ctypes.c_void_p), ("grad_integral_gain", ctypes.c_void_p)]
 
 
+class Policy(ctypes.Structure):
+    """excenv_policy_t: the MLP policy of excenv_sim_policy (one shared parameter array, widths, activation, noise rows, clamp)."""
+
+    _fields_ = [("params", ctypes.c_void_p), ("n_layers", ctypes.c_int32), ("activation", ctypes.c_int32),
+                ("widths", ctypes.c_int32 * (POLICY_MAX_LAYERS + 1)), ("noise", ctypes.c_void_p), ("clip_lo", ctypes.c_double),
+                ("clip_hi", ctypes.c_double)]
+
+
 # the C types of the header's structures (tests/test_native_binding.py compares sizes and field offsets with the host compiler's)
 STRUCTS = {Param: "excenv_param_t", PmsmLut: "excenv_pmsm_lut_t", Props: "excenv_props_t", LaunchOpts: "excenv_launch_opts_t",
            TrajGym: "excenv_traj_gym_t", Control: "excenv_control_t", Feedback: "excenv_feedback_t",
-           FeedbackVjp: "excenv_feedback_vjp_t"}
+           FeedbackVjp: "excenv_feedback_vjp_t", Policy: "excenv_policy_t"}
 
 _vp, _ci, _i32, _i64, _cd = ctypes.c_void_p, ctypes.c_int, ctypes.c_int32, ctypes.c_int64, ctypes.c_double
 _STEP = [_ci, _ci, _ci, _i64, _vp, _vp, _cd, _vp, _vp, _vp, _vp]  # env, solver, dtype, B, props, control, tau, in, action, out, obs
@@ -152,6 +163,8 @@ PROTOTYPES = {
     # env, solver, dtype, B, K, substeps, props, control, obs_stepsize, env_tau, state_in, policy, obs_traj, state_traj, last_state,
     # actions_out, opts, stream
     "excenv_sim_feedback": (_ci, [_ci, _ci, _ci, _i64, _i64, _i32, _vp, _vp, _cd, _cd, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # the arguments of excenv_sim_feedback, `policy` an excenv_policy_t
+    "excenv_sim_policy": (_ci, [_ci, _ci, _ci, _i64, _i64, _i32, _vp, _vp, _cd, _cd, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "excenv_sim_feedback_vjp_workspace_bytes": (_i64, [_ci, _ci, _i64, _i64, _i32, _i64, _ci]),
     "excenv_sim_feedback_vjp_bytes": (_i64, [_ci, _ci, _i32, _i32, _ci, _ci, _ci, _ci]),
     # env, solver, dtype, B, K, substeps, props, control, obs_stepsize, env_tau, call, workspace, workspace_bytes, opts, stream

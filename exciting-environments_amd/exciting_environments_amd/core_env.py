@@ -31,6 +31,7 @@ from ._trajectory import TrajectoryLaunchMixin
 from ._reward_vjp import RewardVjpMixin
 from ._feedback import FeedbackMixin
 from ._feedback_vjp import FeedbackVjpMixin
+from ._policy import PolicyMixin
 from ._linearize import LinearizeMixin
 from ._step_vjp import StepVjpMixin
 from ._vjp import TrajectoryVjpMixin
@@ -49,7 +50,7 @@ def _is_scalar(x) -> bool:
 
 
 class CoreEnvironment(TrajectoryLaunchMixin, TrajectoryVjpMixin, RewardVjpMixin, StepVjpMixin, LinearizeMixin, FeedbackMixin,
-                      FeedbackVjpMixin, ABC):
+                      FeedbackVjpMixin, PolicyMixin, ABC):
     """Core structure of the provided environments (reference core_env.py:15-57).
 
     The simulated systems are physical state-space models dx/dt = f(x(t), u(t)); outputs are

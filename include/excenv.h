@@ -477,6 +477,48 @@ int excenv_sim_feedback(int env, int solver, int dtype, int64_t B, int64_t K, in
                         const excenv_feedback_t* policy, void* obs_traj, void* const* state_traj, void* const* last_state,
                         void* actions_out, const excenv_launch_opts_t* opts, void* stream);
 
+/* ---- policy rollouts: excenv_sim_feedback with a small multi-layer perceptron as the policy record, evaluated INSIDE the one
+ * persistent launch of sim_policy_kernel (an addition, same ABI version: a binder probes for the symbol). Same EXCENV_SEM_STEP
+ * rows, N = K * substeps, OW = O + n_control, obs_n = the saved observation row n (reference columns included). The network has
+ * L = n_layers linear layers, 1 <= L <= EXCENV_POLICY_MAX_LAYERS, of widths d_0 = OW, d_1 .. d_{L-1} (hidden, each
+ * 1 .. EXCENV_POLICY_MAX_WIDTH), d_L = A; L = 1 has no hidden layer. At every action row k, n = k * substeps, per environment:
+ *   x^0 = obs_n
+ *   for l = 1 .. L, for j = 0 .. d_l - 1:
+ *     acc = b_l[j];  acc = fma(W_l[j][i], x^{l-1}[i], acc) for i = 0 .. d_{l-1} - 1, in this order
+ *     x^l[j] = act(acc) for l < L, acc for l == L
+ *   raw[q] = noise[k][q] + x^L[q]                  (one rounded add; without noise raw[q] = x^L[q], no add)
+ *   a[k][q] = min(max(raw[q], clip_lo), clip_hi)   (a NaN passes through; -inf / +inf change nothing)
+ * act is EXCENV_ACT_RELU, (acc < 0) ? 0 : acc, or EXCENV_ACT_TANH (within 5 ulp of tanh); one activation for all hidden layers.
+ * The normalised action a[k] is held for `substeps` steps of excenv_step's arithmetic (PMSM: substeps == 1).
+ *   params      : ONE device array shared by every environment, in the working dtype: for l = 1 .. L in turn W_l row-major
+ *                 [d_l][d_{l-1}] (torch's nn.Linear.weight layout), then b_l [d_l]. Read-only, never copied or repacked.
+ *   noise       : lane-major [K][A][B] (a pre-sampled exploration row per action) or NULL
+ *   obs_traj    : (out) [N+1][OW][B];  state_traj: (out) S pointers to [N+1][B], or NULL;  last_state: (out) S pointers to [B]
+ *   actions_out : (out) the applied normalised actions [K][A][B], or NULL
+ * obs_traj / state_traj / last_state are bit for bit what excenv_sim_ahead returns under EXCENV_SEM_STEP for `actions_out`.
+ * Properties may be per-environment arrays; pmsm_lut selects the saturated model. Never allocates or synchronises. K == 0: row 0
+ * only; B == 0: EXCENV_OK without a launch. excenv_last_launch() reports "sim_policy_kernel". EXCENV_ENULL names a missing pointer
+ * (policy, policy->params, obs_traj, last_state, a state pointer). EXCENV_EINVAL: n_layers outside 1 .. 4, a hidden width outside
+ * 1 .. 64, widths[0] != OW or widths[L] != A, an unknown activation, clip_lo > clip_hi or a NaN bound, PMSM with substeps != 1,
+ * opts->envs_per_lane other than 0 or 1. */
+#define EXCENV_POLICY_MAX_LAYERS 4
+#define EXCENV_POLICY_MAX_WIDTH 64
+#define EXCENV_ACT_RELU 0
+#define EXCENV_ACT_TANH 1
+typedef struct {
+  const void* params;                           /* W_1, b_1, .., W_L, b_L; required */
+  int32_t n_layers;                             /* L */
+  int32_t activation;                           /* EXCENV_ACT_RELU / EXCENV_ACT_TANH, of the hidden layers */
+  int32_t widths[EXCENV_POLICY_MAX_LAYERS + 1]; /* d_0 .. d_L; entries past L are not read */
+  const void* noise;                            /* [K][A][B] or NULL */
+  double clip_lo;                               /* -inf: no lower clamp */
+  double clip_hi;                               /* +inf: no upper clamp */
+} excenv_policy_t;
+int excenv_sim_policy(int env, int solver, int dtype, int64_t B, int64_t K, int32_t substeps, const excenv_props_t* props,
+                      const excenv_control_t* control, double obs_stepsize, double env_tau, const void* const* state_in,
+                      const excenv_policy_t* policy, void* obs_traj, void* const* state_traj, void* const* last_state,
+                      void* actions_out, const excenv_launch_opts_t* opts, void* stream);
+
 /* ---- reverse mode of excenv_sim_feedback: the vector-Jacobian product of one closed-loop trajectory with respect to the initial
  * state, the gains, the feedforward rows and the initial integrator state, from the rows that call saved (additions, same ABI
  * version: a binder probes for the symbols). The forward, at action row k (n = k * substeps, ob = saved observation row n with all

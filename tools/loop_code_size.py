@@ -3,7 +3,8 @@
 the headline loop (PMSM Euler fp32, V = 4, ping-pong: two unrolled solver steps x 4 environments per lane) is close to it and
 any growth — gym outputs on the vector path, a third register set — would fall off that cliff unnoticed (misses are < 1e-5
 today, tools/icache_probe.sh). This tool takes the device code out of the built library, disassembles every
-sim_ahead_kernel / sim_ahead_em_kernel and reports the span of its largest backward branch = the outermost loop — or more: where
+sim_ahead_kernel / sim_ahead_em_kernel (loop_spans(match=...): any other family, "sim_feedback_kernel", "sim_policy_kernel") and
+reports the span of its largest backward branch = the outermost loop — or more: where
 the compiler has moved a cold block behind the loop (the once-per-launch vote of EXCENV_OPT_KEEP_CONSTANT_COLUMNS in the PMSM lean
 kernels) the way back from it is a backward branch across the whole loop, and the figure is then loop + everything up to that block
 (headline: 28.8 KB for a 14.3 KB loop). It stays an UPPER bound of the loop, so the limit still guards what it is meant to. Exit code 1
@@ -65,23 +66,24 @@ def loop_spans(lib=LIB, match="sim_ahead"):
 
 
 def kernel_resources(lib=LIB):
-    """{kernel symbol: {"scratch": private segment bytes per lane, "vgpr": count, "sgpr": count}} from the code objects' metadata
-    notes. A trajectory kernel that starts to spill reloads its registers behind `s_waitcnt vmcnt(0)`, i.e. behind every
+    """{kernel symbol: {"scratch": private segment bytes per lane, "vgpr": count, "sgpr": count, "lds": static LDS bytes per
+    workgroup}} from the code objects' metadata notes (sim_policy_kernel sizes its LDS at the launch: its static figure is 0).
+    A trajectory kernel that starts to spill reloads its registers behind `s_waitcnt vmcnt(0)`, i.e. behind every
     outstanding trajectory store (kernels_emr.hpp: 7.7 -> 7.1 ms when the last spills went): worth failing the build for."""
     out = {}
     for notes in _code_objects(lib, [READELF, "--notes"]):
         cur = {}
         for line in notes.splitlines():
-            m = re.match(r"\s*-?\s*\.(name|private_segment_fixed_size|vgpr_count|sgpr_count):\s*(\S+)", line)
+            m = re.match(r"\s*-?\s*\.(name|private_segment_fixed_size|group_segment_fixed_size|vgpr_count|sgpr_count):\s*(\S+)", line)
             if not m:
                 continue
             k, v = m.group(1), m.group(2).strip("'\"")
             if k == "name" and not v.startswith("_Z"):
                 continue  # argument names
             cur[k] = v
-            if all(x in cur for x in ("name", "private_segment_fixed_size", "vgpr_count", "sgpr_count")):
+            if all(x in cur for x in ("name", "private_segment_fixed_size", "group_segment_fixed_size", "vgpr_count", "sgpr_count")):
                 out[cur["name"]] = {"scratch": int(cur["private_segment_fixed_size"]), "vgpr": int(cur["vgpr_count"]),
-                                    "sgpr": int(cur["sgpr_count"])}
+                                    "sgpr": int(cur["sgpr_count"]), "lds": int(cur["group_segment_fixed_size"])}
                 cur = {}
     return out
 
