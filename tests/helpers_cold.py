@@ -238,6 +238,7 @@ def finite_distance(got, want, cols=(), period=2.0):
 
 # ====================================================================== the reverse cases (tests/test_gpu_cold_reverse.py)
 # Shared with tests/test_cold_paths_host.py, which runs the twin on them, asserts the kink cap and prints the twin's own spread.
+# (The closed loop's reverse mode: feedback_twin_reference at the end of this file.)
 REV_MODELS = [("pendulum", None), ("cartpole", None), ("acrobot", None), ("pmsm", 0), ("pmsm", 1)]
 REV_SOLVERS = ["euler", "rk4", "tsit5"]
 REV_DTYPES = ["float32", "float64"]
@@ -383,3 +384,67 @@ def twin_reference(env_name, deadtime, solver, semantics, dtype, V, sub, K=REV_K
     if len(_TWIN_REF) > 64:
         _TWIN_REF.pop(next(iter(_TWIN_REF)))
     return _TWIN_REF[key]
+
+
+# ====================================================================== the closed loop's reverse mode
+FB_SEED = REV_SEED  # the seed of the policy's inputs (helpers_feedback.feedback_inputs); the states are reverse_setup's
+
+
+def feedback_reverse_subs(env_name):
+    return (1,) if env_name == "pmsm" else (1, 2)
+
+
+_FB_REF = {}
+
+
+def feedback_twin_reference(env_name, deadtime, solver, dtype, sub, uniform, K=REV_K):
+    """twin_reference for `vmap_sim_ahead_feedback_vjp`: the states of reverse_setup (V = 1, B = 326) under the full policy of
+    helpers_feedback.feedback_inputs (per-environment gains, integral action, feedforward, clip), all five cotangents, the float64
+    closed-loop twin (helpers_feedback_vjp.twin_run) on the SPECIAL environments alone. -> dict(idx, kinds, built, spec, inp: the
+    inputs over all B in values the number format represents (st: the special states), group: the cotangents over all B, want:
+    (first gradient, [the others]) on idx in the order state0 leaves, gain, integral gain, feedforward, integrator state, spread: the
+    same one-ulp perturbation of the special angles as twin_reference's, pushed through twin_run, keep, obs: the twin's forward
+    observations on idx). Computed once per form and shared."""
+    import helpers_feedback as hf
+    import helpers_feedback_vjp as hv
+    from helpers_vjp import KINK_MARGIN
+
+    key = (env_name, deadtime, solver, np.dtype(dtype).name, sub, uniform, K)
+    if key in _FB_REF:
+        return _FB_REF[key]
+    npdt = np.dtype(dtype).type
+    kinds = kinds_for(env_name, dtype, reverse=True)
+    spec, built, _ = reverse_setup(env_name, deadtime, dtype, 1, K, uniform, kinds)
+    B, S = built["mask"].shape[0], len(built["special"])
+    idx = np.flatnonzero(built["mask"])
+    r = lambda a: None if a is None else np.asarray(a).astype(npdt).astype(np.float64)
+    raw = hf.feedback_inputs(env_name, spec, B, K, seed=FB_SEED)
+    inp = dict(st=[v.astype(np.float64) for v in built["special"]], gain=r(raw["gain"]), igain=r(raw["igain"]), ff=r(raw["ff"]), z0=r(raw["z0"]),
+               refs=None)
+    O = oracle.ENV_DIMS[oracle.ENV_IDS[env_name]][2]
+    A = oracle.ENV_DIMS[oracle.ENV_IDS[env_name]][1]
+    full = hv.cotangent_groups(np.random.default_rng(5), B, K * sub + 1, O, S, K, A)[0]
+    group = {k: ([r(x) for x in v] if isinstance(v, list) else r(v)) for k, v in full.items()}
+    on = lambda v: [x[idx] for x in v] if isinstance(v, list) else v[idx]
+    sub_group = {k: on(v) for k, v in group.items()}
+
+    def run(leaves):
+        part = dict(inp, st=[v[idx].astype(np.float64) for v in leaves], gain=inp["gain"][idx], igain=inp["igain"][idx], ff=inp["ff"][idx],
+                    z0=inp["z0"][idx])
+        twin, lv, out = hv.twin_run(env_name, spec, solver, part, K, sub)
+        g = hv.twin_grads(lv, out, [sub_group], O)[0]
+        kd = twin.kink_distance()
+        return list(g["state0"]) + [g["gain"], g["igain"], g["ff"], g["z0"]], kd, out["obs"].detach().numpy()
+
+    want, kd, obs = run(built["special"])
+    angles = built["written"].copy()  # "the special angles move by one ulp": the angle leaves only
+    angles[[j for j in range(S) if j not in ANGLE_STATES.get(env_name, [])]] = False
+    up, _, _ = run(one_ulp(built["special"], angles, +1))
+    down, _, _ = run(one_ulp(built["special"], angles, -1))
+    kinds_idx = built["kind"][idx]
+    keep = np.ones(idx.size, dtype=bool) if kd is None else (kd.numpy() >= KINK_MARGIN)
+    _FB_REF[key] = dict(idx=idx, kinds=kinds_idx, built=built, spec=spec, inp=inp, group=group, want=(want[0], want[1:]),
+                        spread=spread_by_kind(up, down, want, kinds_idx, keep), keep=keep, obs=obs)
+    if len(_FB_REF) > 64:
+        _FB_REF.pop(next(iter(_FB_REF)))
+    return _FB_REF[key]

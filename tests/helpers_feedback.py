@@ -157,7 +157,7 @@ def oracle_case(env_name, deadtime, solver):
     return oracle_closed_loop(env_name, solver, props, inp, spec["tau"])
 
 
-def saturated_env(B, dtype, solver, device):
+def saturated_env(B, dtype, solver, device, control_state=None):
     """The saturated PMSM (helpers_lut.saturating_lut) on `device` and its oracle properties in float64 -> (env, props, keep, spec)"""
     import torch
 
@@ -168,7 +168,7 @@ def saturated_env(B, dtype, solver, device):
     lut = saturating_lut()
     solv = {"euler": ex.Euler(), "rk4": ex.RK4(), "tsit5": ex.Tsit5()}[solver]
     env = EnvironmentRegistry.PMSM.make(batch_size=B, saturated=True, motor_variant=MotorVariant.BRUSA, pmsm_lut=lut, solver=solv,
-                                        dtype=dtype, device=device)
+                                        dtype=dtype, device=device, control_state=control_state)
     ep = env.env_properties
     params = {n: getattr(ep.static_params, n) for n in env.PARAM_FIELDS}
     pn = {n: (getattr(ep.physical_normalizations, n).min, getattr(ep.physical_normalizations, n).max) for n in env.STATE_FIELDS}

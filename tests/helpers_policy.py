@@ -20,14 +20,15 @@ def action_dim(env_name):
     return oracle.ENV_DIMS[oracle.ENV_IDS[env_name]][1]
 
 
-def policy_inputs(env_name, spec, hidden, B=B_MAIN, K=K_MAIN, control=None):
+def policy_inputs(env_name, spec, hidden, B=B_MAIN, K=K_MAIN, control=None, seed=SEED):
     """Seeded inputs of one case, float64: dict(st, W, b, noise, refs, widths). States are helpers_vjp.vjp_inputs' (seed 91); then
     from default_rng(7091), in this order: all W_l ~ N(0, 1 / sqrt(d_{l-1})), all b_l ~ U(-0.1, 0.1), noise ~ U(-1.25, 1.25)
-    [B, K, A]; last the references of the controlled fields inside the normalisation box."""
+    [B, K, A]; last the references of the controlled fields inside the normalisation box. seed: another draw of the same
+    distributions (the randomised tests, the second parameter set of the in-place update)."""
     A = action_dim(env_name)
     widths = (obs_width(env_name, control),) + tuple(hidden) + (A,)
-    st, _ = vjp_inputs(env_name, spec, B, max(K, 1), SEED)
-    rng = np.random.default_rng(7000 + SEED)
+    st, _ = vjp_inputs(env_name, spec, B, max(K, 1), seed)
+    rng = np.random.default_rng(7000 + seed)
     W = [rng.normal(0.0, 1.0 / np.sqrt(n), (d, n)) for n, d in zip(widths[:-1], widths[1:])]
     b = [rng.uniform(-0.1, 0.1, d) for d in widths[1:]]
     noise = rng.uniform(-1.25, 1.25, (B, K, A))

@@ -7,7 +7,9 @@
 4. The fp32 reverse comparisons of tests/test_gpu_cold_reverse.py leave out the special environments within KINK_MARGIN of a kink: at
    most KINK_CAP of them (the precedent of tests/test_linearize_host.py; the seed of helpers_cold.REV_SEED is chosen so).
 5. The twin's own spread under one ulp of the special angles — what sets the reverse bounds where it exceeds the existing ones — is
-   computed here and printed, so that it can be read without a GPU."""
+   computed here and printed, so that it can be read without a GPU.
+6. The same for the closed loop's reverse mode (helpers_cold.feedback_twin_reference: the full affine policy over the special states,
+   its clamps counted as kinks): finite gradients, the cap, the spread."""
 import numpy as np
 import pytest
 
@@ -164,3 +166,26 @@ def test_the_twin_runs_on_the_special_inputs_and_its_spread(case):
         assert np.isfinite(ref["want"][0]).all() and (dtype == "float64" or excluded <= KINK_CAP)
     ref = twin_reference(env_name, deadtime, solver, ("ahead", "step")[n % 2], dtype, 1, 1, uniform=uniform_kind(case, kinds, shift=2))
     assert dtype == "float64" or 1.0 - ref["keep"].mean() <= KINK_CAP
+
+
+@pytest.mark.parametrize("case", reverse_cases(), ids=reverse_id)
+def test_the_closed_loop_twin_runs_on_the_special_inputs_and_its_spread(case):
+    """The inputs of tests/test_gpu_cold_reverse.py::test_closed_loop_gradients_with_special_initial_angles through the closed-loop
+    twin alone: finite gradients, the clamp at work, the excluded share of the fp32 comparison under the cap (the policy's clamps
+    count as kinks), the twin's own spread per kind printed."""
+    from helpers_cold import feedback_reverse_subs, feedback_twin_reference
+
+    env_name, deadtime, solver, dtype = case
+    kinds = kinds_for(env_name, dtype, reverse=True)
+    uniform = uniform_kind(case, kinds, shift=3)
+    for sub in feedback_reverse_subs(env_name):
+        ref = feedback_twin_reference(env_name, deadtime, solver, dtype, sub, uniform)
+        flat = np.concatenate([ref["want"][0].ravel()] + [g.ravel() for g in ref["want"][1]])
+        assert np.isfinite(flat).all() and np.abs(flat).max() > 0 and np.isfinite(ref["obs"]).all()
+        assert set(ref["kinds"]) == set(kinds)
+        assert all_inside(env_name, ref["spec"], ref["built"]["plain"], dtype) is None
+        excluded = 1.0 - ref["keep"].mean()
+        print(f"cold reverse closed-loop twin {reverse_id(case)} substeps={sub} K={REV_K} uniform={uniform}: excluded {excluded:.4f}, "
+              "spread under one ulp " + ", ".join(f"{k} {v:.2e}" for k, v in ref["spread"].items()))
+        if dtype == "float32":
+            assert excluded <= KINK_CAP, (sub, excluded)

@@ -368,3 +368,43 @@ def test_closed_loop_with_special_initial_angles(env_name, deadtime, solver, dty
           f"{'bit-equal' if same else 'DIFFER'}; dynamics bit-equal to the open-loop launch; policy within its rounding bounds")
     assert same and moved
     assert bool(torch.isfinite(runs["special"]["obs"]).all())
+
+
+@pytest.mark.parametrize("env_name,deadtime,solver,dtype", FEEDBACK_CASES)
+def test_policy_rollout_with_special_initial_angles(env_name, deadtime, solver, dtype):
+    """sim_policy_kernel on helpers_policy.main_case (network N1, the activation alternating with the case index) with the angle kinds
+    in the initial state: the helpers of tests/test_gpu_policy.py as they are (the open-loop kernel on the returned actions bit for
+    bit; ReLU actions bit for bit the contract on the returned observation rows, tanh actions within the forward bound), and the
+    bystanders of (a): observations and actions of every other environment have the bits of the run on the plain inputs.
+    The launch is 64 wide (policy.hpp POLICY_BLOCK), one wavefront per workgroup, so the lane pattern of special_envs(B, 1) puts the
+    uniform special wave into workgroup 3 and mixed waves into workgroups 0 and 1 (and the tail's, workgroup 5); workgroup 2 is clean."""
+    import helpers_policy as hp
+    from helpers import make_env
+    from test_gpu_policy import check_dynamics, check_policy, rollout
+
+    tdt = getattr(torch, dtype)
+    n = FEEDBACK_CASES.index((env_name, deadtime, solver, dtype))
+    activation = hp.ACTIVATIONS[n % len(hp.ACTIVATIONS)]
+    spec, inp = hp.main_case(env_name, deadtime, "N1")
+    kinds = [k for k in kinds_for(env_name, dtype, reverse=True) if k != "zero"]
+    uniform = kinds[n % len(kinds)]
+    built = build(env_name, spec, dtype, hp.B_MAIN, 1, uniform, seed=hp.SEED, reverse=True, plain=[np.asarray(v).astype(dtype) for v in inp["st"]],
+                  kinds=kinds)
+    waves = wave_summary(built["mask"], 1)
+    assert waves[:4] == ["mixed", "mixed", "clean", "uniform"] and waves[-1] == "mixed", waves
+    runs = {}
+    for which in ("special", "plain"):
+        data = dict(inp, st=[v.astype(np.float64) for v in built[which]])
+        env, _, _, _ = make_env(env_name, hp.B_MAIN, tdt, solver, spec=spec)
+        run = rollout(env, data, activation, hp.K_MAIN, hp.substeps_of(env_name), spec["tau"])
+        check_dynamics(run)
+        check_policy(run, data)
+        runs[which] = run
+    calm = torch.as_tensor(~built["mask"], device=runs["special"]["obs"].device)
+    same = all(torch.equal(runs["special"][n][calm], runs["plain"][n][calm]) for n in ("obs", "actions"))
+    moved = not torch.equal(runs["special"]["obs"][~calm], runs["plain"]["obs"][~calm])
+    print(f"cold forward policy {env_name} deadtime={deadtime} {solver} {dtype} {activation}: sim_policy_kernel; uniform kind {uniform}; "
+          f"bystanders {'bit-equal' if same else 'DIFFER'}; dynamics bit-equal to the open-loop launch; policy "
+          f"{'bit-equal to the exact contract' if activation == 'relu' else 'within its forward bound'}")
+    assert same and moved
+    assert bool(torch.isfinite(runs["special"]["obs"]).all())

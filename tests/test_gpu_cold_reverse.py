@@ -21,6 +21,8 @@ Every launch is made twice, on the `special` inputs and on `plain` ones (an ordi
 (c) `mod` and `quad64` alone, K = 1 under "step": the Jacobian is evaluated at the caller's own angle and nothing wraps it first.
     sincos_lean's former `(int)n` quadrant gave sin and cos of such an angle with the wrong sign or swapped (errors of 2.0,
     tools/sincos_lean_restate.c): an error of the Jacobian's own size.
+(d) the closed loop: vmap_sim_ahead_feedback_vjp under the full policy, (a) and (b) on all five gradients, and one gain set for all
+    as the deterministic batch sum of the per-environment launch on the same special inputs.
 Every case prints its launch name, the bystander verdict and per kind the distance, its bound and the rule that set it."""
 import numpy as np
 import pytest
@@ -322,4 +324,50 @@ def test_reward_backward_with_an_angle_control_at_special_angles(env_name, dtype
             problems.append(f"{k}: distance {d:.3e}, bound {bound:.3e} ({rule})")
     print(f"cold reverse reward {env_name} {dtype} control={control}: {launch}; bystanders {'bit-equal' if same else 'DIFFER'}; " + "; ".join(report))
     assert same, "bystanders differ between the special and the plain launch"
+    assert not problems, "\n".join(problems)
+
+
+# ------------------------------------------------------------------------------------------------- the closed loop's reverse mode
+@pytest.mark.parametrize("case", reverse_cases(), ids=reverse_id)
+def test_closed_loop_gradients_with_special_initial_angles(case):
+    """vmap_sim_ahead_feedback_vjp (feedback_z_rows_kernel, sim_feedback_vjp_kernel, feedback_gain_grad_kernel) with every reverse kind in
+    the initial state: B = 326, K = 3, substeps 1 and 2 (PMSM: 1), the full policy (per-environment gains, integral action,
+    feedforward, clip), all five cotangents. (a) bystanders: grad_state0, grad_gain, grad_integral_gain, grad_ff and grad_z0 of every
+    non-special environment have the same bits in the `special` and the `plain` launch; (b) the special environments against the
+    float64 closed-loop twin under _judge's rules as they are (1e-8 in fp64, 32 x the forward floor in fp32, per kind, or 16 x the
+    twin's own spread under one ulp of the special angles: helpers_cold.feedback_twin_reference). The fp32 forward floor is taken
+    over the rows the launch computed (1 .. N). With row 0 in it — the caller's own unwrapped angle, normalised: 3e7 in the `mod`
+    environments — obs_floor's scale is that number, the floor of "all special environments" becomes 5.3e-8 (the rounding of 3e7,
+    no forward error at all), and a `zero` environment at omega = its lower bound (distance 1.7e-6 .. 3.3e-6 in three cases, below
+    32 fp32 epsilons) was held to 1.69e-6 by the angle of another environment.
+    One gain set for all, once per case: the bystander rule cannot apply to a sum over the batch; instead the sum is, bit for bit,
+    excenv_param_grad_sum of the per-environment launch on the same special inputs (and every other gradient that launch's)."""
+    from helpers_cold import feedback_reverse_subs, feedback_twin_reference
+    from test_gpu_feedback_vjp import assert_batch_sum_identity, explicit, forward
+
+    env_name, deadtime, solver, dtype = case
+    tdt = getattr(torch, dtype)
+    uniform = uniform_kind(case, kinds_for(env_name, dtype, reverse=True), shift=3)
+    flat = lambda g: list(g["state0"]) + [g["gain"], g["igain"], g["ff"], g["z0"]]
+    problems = []
+    for n, sub in enumerate(feedback_reverse_subs(env_name)):
+        ref = feedback_twin_reference(env_name, deadtime, solver, dtype, sub, uniform)
+        spec, built, inp, group = ref["spec"], ref["built"], ref["inp"], ref["group"]
+        B = built["mask"].shape[0]
+        got = {}
+        for which in ("special", "plain"):
+            data = dict(inp, st=[v.astype(np.float64) for v in built[which]])
+            env, _, _, _ = make_env(env_name, B, tdt, solver, spec=spec)
+            run = forward(env, data, REV_K, sub, spec["tau"])
+            got[which] = (flat(explicit(run, group)), run["obs"].cpu().numpy().astype(np.float64))
+            assert env.last_feedback_vjp_cotangents == dict(obs=True, states=[True] * env.physical_state_dim,
+                                                            last_state=[True] * env.physical_state_dim, actions=True, z=True)
+            if which == "special" and n == 0:  # one gain set for all, on the special inputs
+                one = dict(data, gain=inp["gain"][0], igain=inp["igain"][0])
+                run_b = forward(env, one, REV_K, sub, spec["tau"])
+                assert_batch_sum_identity(run_b, group, explicit(run_b, group), f"cold reverse {reverse_id(case)} substeps={sub} one gain set for all")
+        # the forward floor over the rows the launch computed: row 0 is the caller's own state normalised, an unwrapped angle of 3e7 pi
+        # there sets the scale of obs_floor for every kind and says nothing about the forward error (as _step_vjp_pair: the new row)
+        problems += _judge(f"{reverse_id(case)} closed loop substeps={sub} K={REV_K} uniform={uniform}", dict(ref, obs=ref["obs"][:, 1:]), dtype,
+                           env_name, got["special"][0], got["plain"][0], got["special"][1][:, 1:], "sim_feedback_vjp_kernel")
     assert not problems, "\n".join(problems)

@@ -134,19 +134,23 @@ def test_independent_closed_loop_in_fp64(env_name, deadtime, solver):
                       f"fp64 {env_name} deadtime {deadtime} {solver}")
 
 
-def check_independent(run, inp, props, want, env_name, solver, tau, label):
-    """Test 3 on one fp64 run: observations, actions and integrator against the oracle loop `want`, within the measured tolerance"""
+def check_independent(run, inp, props, want, env_name, solver, tau, label, control=None):
+    """Test 3 on one fp64 run: observations, actions and integrator against the oracle loop `want`, within the measured tolerance
+    -> the largest distance / tolerance. control: the controlled fields, whose references inp["refs"] the open-loop oracle shows too;
+    without an integrator there is no z to compare."""
     got_obs = run["obs"].cpu().numpy()
     acts = run["actions"].cpu().numpy()
-    open_obs, _, _ = oracle.sim_ahead(env_name, solver, inp["st"], acts, props, tau, substeps=run["sub"], semantics=oracle.SEM_STEP)
+    ctl = [(n, inp["refs"][n]) for n in control] if control else None
+    open_obs, _, _ = oracle.sim_ahead(env_name, solver, inp["st"], acts, props, tau, substeps=run["sub"], semantics=oracle.SEM_STEP, control=ctl)
     d_open = obs_floor(got_obs, open_obs, env_name)
     d_closed = obs_floor(got_obs, want["obs"], env_name)
-    d_act = float(np.max(np.abs(acts - want["actions"])))
-    d_z = float(np.max(np.abs(run["z"].cpu().numpy() - want["z"])))
+    d_act = float(np.max(np.abs(acts - want["actions"]), initial=0.0))
+    d_z = float(np.max(np.abs(run["z"].cpu().numpy() - want["z"]))) if want["z"] is not None else 0.0
     tol = max(100.0 * d_open, 1e-12)
     print(f"{label}: open loop vs oracle {d_open:.3e}, closed loop vs oracle {d_closed:.3e}, actions {d_act:.3e}, "
           f"integrator {d_z:.3e}, allowed {tol:.3e}")
     assert d_closed <= tol and d_act <= tol and d_z <= tol
+    return max(d_closed, d_act, d_z) / tol
 
 
 @pytest.mark.parametrize("dtype", DTYPES, ids=["fp32", "fp64"])

@@ -367,11 +367,23 @@ def test_broadcast_gains_are_the_batch_sum_of_the_per_environment_result(env_nam
     env = run["env"]
     B, A, OW = env.batch_size, env.action_dim, env._obs_dim()
     assert tuple(got["gain"].shape) == (A, OW) and tuple(got["igain"].shape) == (A, OW)
+    assert_batch_sum_identity(run, group, got, env_name)
+
+
+def assert_batch_sum_identity(run, group, got, label):
+    """One gain set for all: its gradients equal, bit for bit, excenv_param_grad_sum of the per-environment gradients of the same
+    gains, one copy per environment, and every other gradient is the per-environment launch's -> that launch's result"""
+    env = run["env"]
+    B, A, OW = env.batch_size, env.action_dim, env._obs_dim()
     # the same gains, one copy per environment: per-environment gradients, summed by excenv_param_grad_sum
     rep = dict(run)
-    rep["gain"], rep["igain"] = run["gain"][None].expand(B, A, OW).contiguous(), run["igain"][None].expand(B, A, OW).contiguous()
+    rep["gain"] = run["gain"][None].expand(B, A, OW).contiguous()
+    rep["igain"] = None if run["igain"] is None else run["igain"][None].expand(B, A, OW).contiguous()
     per = explicit(rep, group)
     for name, j in (("gain", 1), ("igain", 2)):
+        if per["raw"][j] is None:
+            assert got["raw"][j] is None
+            continue
         t = per["raw"][j]  # [B, A, OW] over lane-major memory
         leaves = [t[:, q, o] for q in range(A) for o in range(OW)]
         assert all(l.is_contiguous() for l in leaves)
@@ -380,11 +392,13 @@ def test_broadcast_gains_are_the_batch_sum_of_the_per_environment_result(env_nam
             sums += env._param_grad_sum(leaves[c:c + _native.MAX_STATIC])
         summed = torch.stack(sums).reshape(A, OW)
         same = torch.equal(summed, got["raw"][j])
-        print(f"{env_name} {name}: broadcast result == excenv_param_grad_sum of the per-environment result: {same}")
+        print(f"{label} {name}: broadcast result == excenv_param_grad_sum of the per-environment result: {same}")
         assert same
     for a, b in zip(per["state0"], got["state0"]):
         assert np.array_equal(a, b)
-    assert np.array_equal(per["ff"], got["ff"]) and np.array_equal(per["z0"], got["z0"])
+    assert np.array_equal(per["ff"], got["ff"])
+    assert (per["z0"] is None and got["z0"] is None) or np.array_equal(per["z0"], got["z0"])
+    return per
 
 
 def test_mixed_pair_broadcast_gain_with_per_environment_integral_gain():

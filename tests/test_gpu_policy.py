@@ -5,13 +5,15 @@
 2. policy, from the RETURNED observation rows: (a) ReLU networks and N0: the actions bit for bit the contract evaluated with an exact
    CPU fused multiply-add (helpers_policy.fma_exact), every environment; (b) tanh networks: every action entry within the forward
    bound of helpers_policy.policy_bounds and nothing more; (c) the device's tanh within 5 ulp of float64 numpy's (asserted as
-   10 u |tanh|) through a network whose every multiply-add is exact;
+   10 u |tanh|) through a network whose every multiply-add is exact, from |x| ~ 1e-13 to beyond the overflow of exp(2 x);
 3. the independent fp64 closed loop (numpy policy over oracle.step) within 100 x the distance the open-loop launch shows against
    oracle.sim_ahead on the same actions (floor 1e-12 of full scale): tests/test_gpu_feedback.py check_independent's rule;
 4. forms: N2, N0 and N3, per-environment properties, control columns fed into the network, no noise, no clamp, a plain noise tensor,
    no state trajectory, K = 1, B = 1, K = 0, B = 64 exactly;
 5. all-zero parameters, no clamp: the open-loop launch on the noise tensor, bit for bit;
-6. `MLPPolicy.from_torch`: the torch module's float64 forward on the returned observation rows within bound (b) of the actions.
+6. `MLPPolicy.from_torch`: the torch module's float64 forward on the returned observation rows within bound (b) of the actions;
+7. `policy.params` updated in place between two launches (same stream, and on a side stream between two wait_stream calls): the next
+   launch computes with the new values, bit for bit.
 
 Measured on an MI355X (largest error / bound of 2b; distances of 3): see DESIGN.md §4.13."""
 import functools
@@ -157,12 +159,17 @@ def test_tanh_actions_lie_within_the_forward_bound(env_name, deadtime, solver, d
     check_bound(run, inp)
 
 
-@pytest.mark.parametrize("scale", [4.0, 2.0 ** -10], ids=["s=4", "s=2^-10"])
+TANH_REACH = {2.0 ** 7: 44.0, 2.0 ** 9: 355.0}  # where exp(2 x) overflows in fp32 / fp64: a tanh built on it goes wrong beyond
+
+
+@pytest.mark.parametrize("scale", [4.0, 2.0 ** -10, 2.0 ** 7, 2.0 ** 9, 2.0 ** -40], ids=["s=4", "s=2^-10", "s=2^7", "s=2^9", "s=2^-40"])
 @pytest.mark.parametrize("dtype", DTYPES, ids=DTYPE_IDS)
 @pytest.mark.parametrize("env_name,deadtime", [("pendulum", None), ("pmsm", 1)])
 def test_the_device_tanh_is_within_five_ulp(env_name, deadtime, dtype, scale):
     """OW -> OW -> A with W_1 = s I, b = 0, W_2 one-hot, no noise, no clamp: every fma is exact, so a[q] = tanh_device(s obs[q]).
-    Each entry within 5 ulp of float64 np.tanh, asserted as 10 u |tanh|: the feature's requirement (OpenCL's conformance bound)."""
+    Each entry within 5 ulp of float64 np.tanh, asserted as 10 u |tanh|: the feature's requirement (OpenCL's conformance bound).
+    s = 2^7 and 2^9 reach |x| > 44 and > 355, where exp(2 x) overflows in fp32 and fp64; s = 2^-40 the linear end (the products are
+    normal numbers in both formats). No NaN, no inf, |a| <= 1 at every scale."""
     spec = hp.case_spec(env_name, deadtime)
     env, _, _, _ = make_env(env_name, hp.B_MAIN, dtype, "euler", spec=spec)
     OW, A = env._obs_dim(), env.action_dim
@@ -180,6 +187,9 @@ def test_the_device_tanh_is_within_five_ulp(env_name, deadtime, dtype, scale):
           f"|x| up to {float(np.abs(scale * x).max()):.3g}")
     assert np.all(err <= 10.0 * u * np.abs(want))
     assert np.any(want != 0)
+    assert np.isfinite(got).all() and float(np.abs(got).max()) <= 1.0
+    if scale in TANH_REACH:
+        assert float(np.abs(scale * x).max()) > TANH_REACH[scale], float(np.abs(scale * x).max())
     check_dynamics(run)
 
 
@@ -196,17 +206,20 @@ def test_independent_closed_loop_in_fp64(env_name, deadtime, solver, activation)
                       f"fp64 {env_name} deadtime {deadtime} {solver} {activation}")
 
 
-def check_independent(run, inp, props, want, env_name, solver, tau, label):
-    """Test 3 on one fp64 run: observations and actions against the oracle loop `want`, within the measured tolerance"""
+def check_independent(run, inp, props, want, env_name, solver, tau, label, control=None):
+    """Test 3 on one fp64 run: observations and actions against the oracle loop `want`, within the measured tolerance -> the largest
+    distance / tolerance. control: the controlled fields, whose references inp["refs"] the open-loop oracle shows too."""
     got_obs = run["obs"].cpu().numpy()
     acts = run["actions"].cpu().numpy()
-    open_obs, _, _ = oracle.sim_ahead(env_name, solver, inp["st"], acts, props, tau, substeps=run["sub"], semantics=oracle.SEM_STEP)
+    ctl = [(n, inp["refs"][n]) for n in control] if control else None
+    open_obs, _, _ = oracle.sim_ahead(env_name, solver, inp["st"], acts, props, tau, substeps=run["sub"], semantics=oracle.SEM_STEP, control=ctl)
     d_open = obs_floor(got_obs, open_obs, env_name)
     d_closed = obs_floor(got_obs, want["obs"], env_name)
-    d_act = float(np.max(np.abs(acts - want["actions"])))
+    d_act = float(np.max(np.abs(acts - want["actions"]), initial=0.0))
     tol = max(100.0 * d_open, 1e-12)
     print(f"{label}: open loop vs oracle {d_open:.3e}, closed loop vs oracle {d_closed:.3e}, actions {d_act:.3e}, allowed {tol:.3e}")
     assert d_closed <= tol and d_act <= tol
+    return max(d_closed, d_act) / tol
 
 
 @pytest.mark.parametrize("activation", hp.ACTIVATIONS)
@@ -394,3 +407,49 @@ def test_a_torch_module_is_the_policy(env_name, deadtime, dtype, activation):
     print(f"torch module: largest error / bound {float(np.max(err / np.maximum(bound, 1e-300))):.3f}")
     assert np.all(err <= bound)
     assert np.all(np.abs(mine - want) <= bound)  # torch's float64 forward and the restatement: the same function
+
+
+# ---- 7. the parameters are read in place -------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("side_stream", [False, True], ids=["same_stream", "side_stream"])
+@pytest.mark.parametrize("net", ["N1", "N2"])
+@pytest.mark.parametrize("dtype", DTYPES, ids=DTYPE_IDS)
+@pytest.mark.parametrize("env_name,deadtime", FORM_CASES)
+def test_parameters_updated_in_place_are_the_next_launchs(env_name, deadtime, dtype, net, side_stream):
+    """A training loop updates `policy.params` in place between launches. The policy is built on the environment's device in its
+    dtype, so the kernel's scalar loads read `policy.params` itself. Roll out, `policy.params.copy_(second set)`, roll out again with
+    no synchronisation in between: the second run's actions are the contract on the SECOND set bit for bit (check_exact), the bits of a
+    fresh MLPPolicy built from the second set, and not the first run's. side_stream: the update is enqueued on a second stream
+    between two `wait_stream` calls, INTEGRATION.md's stream discipline, nothing more."""
+    env, spec = _form_env(env_name, deadtime, dtype)
+    sub = hp.substeps_of(env_name)
+    first = hp.policy_inputs(env_name, spec, hp.NETS[net])
+    other = hp.policy_inputs(env_name, spec, hp.NETS[net], seed=hp.SEED + 1)
+    second = dict(first, W=other["W"], b=other["b"])  # the same states and noise under the second parameter set
+    policy = excenvs.MLPPolicy(first["W"], first["b"], "relu", device=env.device, dtype=dtype)
+    assert policy.on(env.device, dtype).data_ptr() == policy.params.data_ptr()
+    fresh = excenvs.MLPPolicy(second["W"], second["b"], "relu", device=env.device, dtype=dtype)
+    new_params = fresh.params.clone()
+    state = to_state(env, first["st"])
+    noise = env.new_actions_buffer(hp.K_MAIN)
+    noise.copy_(_dev(first["noise"], env))
+    launch = lambda p: env.vmap_sim_ahead_policy(state, p, hp.K_MAIN, spec["tau"], spec["tau"] * sub, noise=noise)
+    obs1, _, _, act1 = launch(policy)
+    if side_stream:
+        main, side = torch.cuda.current_stream(), torch.cuda.Stream()
+        side.wait_stream(main)
+        with torch.cuda.stream(side):
+            policy.params.copy_(new_params)
+        main.wait_stream(side)
+    else:
+        policy.params.copy_(new_params)
+    obs2, states2, last2, act2 = launch(policy)
+    assert policy.on(env.device, dtype).data_ptr() == policy.params.data_ptr()
+    obs3, _, _, act3 = launch(fresh)
+    torch.cuda.synchronize()
+    run = dict(env=env, state=state, obs=obs2, states=states2, last=last2, actions=act2, K=hp.K_MAIN, sub=sub, tau=spec["tau"],
+               activation="relu", noise=True, clip=hp.CLIP)
+    check_exact(run, second)
+    assert torch.equal(act2, act3) and torch.equal(obs2, obs3)
+    assert not torch.equal(act2, act1)
+    print(f"in-place update {env_name} {dtype} {net} {'side stream' if side_stream else 'same stream'}: second run == the fresh "
+          f"policy's bits; differs from the first run in {float((act2 != act1).float().mean()):.3f} of the action entries")
