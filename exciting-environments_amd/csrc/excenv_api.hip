@@ -124,6 +124,35 @@ static int check_broadcast_props(const char* fn, int env, const excenv_props_t* 
   return EXCENV_OK;
 }
 
+// What the closed-loop calls (excenv_sim_feedback, excenv_sim_policy, excenv_sim_feedback_vjp) check alike, in parts because each
+// checks its policy or call record and the control block in between, in its own order. The head:
+static int check_closed_loop_head(const char* fn, int env, int solver, int dtype, int64_t B, int64_t K, int32_t substeps) {
+  if (int rc = check_common(fn, env, solver, dtype, B)) return rc;
+  if (K < 0 || substeps < 1) { set_error("%s: bad K=%lld or substeps=%d", fn, (long long)K, substeps); return EXCENV_EINVAL; }
+  return EXCENV_OK;
+}
+// The arguments a forward rollout cannot do without
+static int check_rollout_pointers(const char* fn, const excenv_props_t* props, const void* state_in, const void* obs_traj, const void* last_state) {
+  if (!props) { set_error("%s: props is NULL", fn); return EXCENV_ENULL; }
+  if (!state_in) { set_error("%s: state_in is NULL", fn); return EXCENV_ENULL; }
+  if (!obs_traj) { set_error("%s: obs_traj is NULL", fn); return EXCENV_ENULL; }
+  if (!last_state) { set_error("%s: last_state is NULL", fn); return EXCENV_ENULL; }
+  return EXCENV_OK;
+}
+// The tail: the launch options, the one form these kernels have, one step per action row for the PMSM
+static int check_closed_loop_tail(const char* fn, int env, int32_t substeps, const excenv_launch_opts_t*& opts) {
+  if (int rc = check_opts(fn, opts)) return rc;
+  if (opts->envs_per_lane > 1) {
+    set_error("%s: opts.envs_per_lane = %d is not available (this kernel has the one-environment-per-lane form only)", fn, opts->envs_per_lane);
+    return EXCENV_EINVAL;
+  }
+  if (env == EXCENV_PMSM && substeps != 1) {
+    set_error("%s: PMSM: obs_stepsize must equal action_stepsize (substeps = %d; reference pmsm_env.py:787)", fn, substeps);
+    return EXCENV_EINVAL;
+  }
+  return EXCENV_OK;
+}
+
 }  // namespace excenv
 
 using namespace excenv;
@@ -663,26 +692,14 @@ int excenv_sim_feedback(int env, int solver, int dtype, int64_t B, int64_t K, in
                         const excenv_feedback_t* policy, void* obs_traj, void* const* state_traj, void* const* last_state,
                         void* actions_out, const excenv_launch_opts_t* opts, void* stream) {
   const char* fn = "excenv_sim_feedback";
-  if (int rc = check_common(fn, env, solver, dtype, B)) return rc;
-  if (K < 0 || substeps < 1) { set_error("%s: bad K=%lld or substeps=%d", fn, (long long)K, substeps); return EXCENV_EINVAL; }
-  if (!props) { set_error("%s: props is NULL", fn); return EXCENV_ENULL; }
-  if (!state_in) { set_error("%s: state_in is NULL", fn); return EXCENV_ENULL; }
-  if (!obs_traj) { set_error("%s: obs_traj is NULL", fn); return EXCENV_ENULL; }
-  if (!last_state) { set_error("%s: last_state is NULL", fn); return EXCENV_ENULL; }
+  if (int rc = check_closed_loop_head(fn, env, solver, dtype, B, K, substeps)) return rc;
+  if (int rc = check_rollout_pointers(fn, props, state_in, obs_traj, last_state)) return rc;
   {
     char why[256];
     if (int rc = feedback_policy_refusal(policy, B, why, sizeof(why))) { set_error("%s", why); return rc; }
   }
   if (int rc = check_control(fn, env, control)) return rc;
-  if (int rc = check_opts(fn, opts)) return rc;
-  if (opts->envs_per_lane > 1) {
-    set_error("%s: opts.envs_per_lane = %d is not available (this kernel has the one-environment-per-lane form only)", fn, opts->envs_per_lane);
-    return EXCENV_EINVAL;
-  }
-  if (env == EXCENV_PMSM && substeps != 1) {
-    set_error("%s: PMSM: obs_stepsize must equal action_stepsize (substeps = %d; reference pmsm_env.py:787)", fn, substeps);
-    return EXCENV_EINVAL;
-  }
+  if (int rc = check_closed_loop_tail(fn, env, substeps, opts)) return rc;
   int trc;
   const EnvVTable* t = table_for(env, props, &trc);
   if (!t) return trc;
@@ -712,23 +729,14 @@ int excenv_sim_feedback_vjp(int env, int solver, int dtype, int64_t B, int64_t K
                             const excenv_feedback_vjp_t* call, void* workspace, int64_t workspace_bytes,
                             const excenv_launch_opts_t* opts, void* stream) {
   const char* fn = "excenv_sim_feedback_vjp";
-  if (int rc = check_common(fn, env, solver, dtype, B)) return rc;
-  if (K < 0 || substeps < 1) { set_error("%s: bad K=%lld or substeps=%d", fn, (long long)K, substeps); return EXCENV_EINVAL; }
+  if (int rc = check_closed_loop_head(fn, env, solver, dtype, B, K, substeps)) return rc;
   if (int rc = check_reverse_props(fn, props)) return rc;
   {
     char why[256];
     if (int rc = feedback_vjp_refusal(call, B, K, why, sizeof(why))) { set_error("%s", why); return rc; }
   }
   if (int rc = check_control(fn, env, control)) return rc;
-  if (int rc = check_opts(fn, opts)) return rc;
-  if (opts->envs_per_lane > 1) {
-    set_error("%s: opts.envs_per_lane = %d is not available (this kernel has the one-environment-per-lane form only)", fn, opts->envs_per_lane);
-    return EXCENV_EINVAL;
-  }
-  if (env == EXCENV_PMSM && substeps != 1) {
-    set_error("%s: PMSM: obs_stepsize must equal action_stepsize (substeps = %d; reference pmsm_env.py:787)", fn, substeps);
-    return EXCENV_EINVAL;
-  }
+  if (int rc = check_closed_loop_tail(fn, env, substeps, opts)) return rc;
   if (int rc = check_broadcast_props(fn, env, props)) return rc;
   const EnvVTable* t = table_public(env);
   const int64_t need = feedback_vjp_workspace_bytes(t->A, t->O + (control ? control->n_control : 0), dtype == EXCENV_F64 ? 8 : 4, B, K,
@@ -747,27 +755,15 @@ int excenv_sim_policy(int env, int solver, int dtype, int64_t B, int64_t K, int3
                       const excenv_policy_t* policy, void* obs_traj, void* const* state_traj, void* const* last_state,
                       void* actions_out, const excenv_launch_opts_t* opts, void* stream) {
   const char* fn = "excenv_sim_policy";
-  if (int rc = check_common(fn, env, solver, dtype, B)) return rc;
-  if (K < 0 || substeps < 1) { set_error("%s: bad K=%lld or substeps=%d", fn, (long long)K, substeps); return EXCENV_EINVAL; }
-  if (!props) { set_error("%s: props is NULL", fn); return EXCENV_ENULL; }
-  if (!state_in) { set_error("%s: state_in is NULL", fn); return EXCENV_ENULL; }
-  if (!obs_traj) { set_error("%s: obs_traj is NULL", fn); return EXCENV_ENULL; }
-  if (!last_state) { set_error("%s: last_state is NULL", fn); return EXCENV_ENULL; }
+  if (int rc = check_closed_loop_head(fn, env, solver, dtype, B, K, substeps)) return rc;
+  if (int rc = check_rollout_pointers(fn, props, state_in, obs_traj, last_state)) return rc;
   if (int rc = check_control(fn, env, control)) return rc;  // (before the policy: its first width is O + n_control)
   {
     char why[256];
     const EnvVTable* d = table_public(env);
     if (int rc = policy_refusal(policy, d->O + (control ? control->n_control : 0), d->A, why, sizeof(why))) { set_error("%s", why); return rc; }
   }
-  if (int rc = check_opts(fn, opts)) return rc;
-  if (opts->envs_per_lane > 1) {
-    set_error("%s: opts.envs_per_lane = %d is not available (this kernel has the one-environment-per-lane form only)", fn, opts->envs_per_lane);
-    return EXCENV_EINVAL;
-  }
-  if (env == EXCENV_PMSM && substeps != 1) {
-    set_error("%s: PMSM: obs_stepsize must equal action_stepsize (substeps = %d; reference pmsm_env.py:787)", fn, substeps);
-    return EXCENV_EINVAL;
-  }
+  if (int rc = check_closed_loop_tail(fn, env, substeps, opts)) return rc;
   int trc;
   const EnvVTable* t = table_for(env, props, &trc);
   if (!t) return trc;

@@ -1,29 +1,12 @@
 // Closed-loop trajectories: what one excenv_sim_feedback call launches. Host-only and free of HIP, like step_jac.hpp: the call record,
 // what the entry point refuses about the policy before any launch and the name of sim_feedback_kernel (kernels_feedback.hpp).
 #pragma once
-#include <cstdint>
-#include <cstdio>
-#include "../../include/excenv.h"
+#include "closed_loop_call.hpp"
 
 namespace excenv {
 
-// The validated call (excenv_api.hip): K action rows of `substeps` solver steps each for B environments, every action computed inside
-// the launch from the observation row saved at its start (include/excenv.h excenv_feedback_t).
-struct FeedbackCall {
-  int solver, dtype;
-  int64_t B, K;
-  int32_t substeps;
-  const excenv_props_t* props;
-  const excenv_control_t* control;  // nullptr when n_control == 0
-  double obs_stepsize, env_tau;     // the solver's step and the environment's tau (PMSM's dead-time advance)
-  const void* const* state_in;      // S pointers
-  const excenv_feedback_t* policy;
-  void* obs_traj;                   // [N + 1][O + n_control][B]
-  void* const* state_traj;          // S pointers to [N + 1][B], or nullptr
-  void* const* last_state;          // S pointers to [B]
-  void* actions_out;                // [K][A][B] or nullptr
-  void* stream;                     // hipStream_t
-};
+// The validated call (closed_loop_call.hpp) with the affine policy record (include/excenv.h excenv_feedback_t)
+using FeedbackCall = ClosedLoopCall<excenv_feedback_t>;
 
 // sim_feedback_kernel<M, T, SOLVER> exists for the seven models (the saturated PMSM included), the three solvers and both element
 // types, one environment per lane: the only form, so excenv_launch_opts_t.envs_per_lane must be 0 (auto) or 1.
@@ -44,12 +27,7 @@ inline int feedback_policy_refusal(const excenv_feedback_t* p, int64_t B, char* 
                   (long long)p->gain_batch);
     return EXCENV_EINVAL;
   }
-  if (!(p->clip_lo <= p->clip_hi)) {
-    std::snprintf(msg, n, "%s: policy->clip_lo = %g and policy->clip_hi = %g are not an interval (-inf / +inf: no clamp)", fn, p->clip_lo,
-                  p->clip_hi);
-    return EXCENV_EINVAL;
-  }
-  return EXCENV_OK;
+  return clip_refusal(fn, p->clip_lo, p->clip_hi, msg, n);
 }
 
 }  // namespace excenv

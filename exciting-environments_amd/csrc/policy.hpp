@@ -2,29 +2,12 @@
 // entry point refuses about the policy before any launch, the layout of the parameter array, the dynamic LDS of a launch and the
 // name of sim_policy_kernel (kernels_policy.hpp).
 #pragma once
-#include <cstdint>
-#include <cstdio>
-#include "../../include/excenv.h"
+#include "closed_loop_call.hpp"
 
 namespace excenv {
 
-// The validated call (excenv_api.hip): K action rows of `substeps` solver steps each for B environments, every action computed inside
-// the launch by a small MLP on the observation row saved at its start (include/excenv.h excenv_policy_t).
-struct PolicyCall {
-  int solver, dtype;
-  int64_t B, K;
-  int32_t substeps;
-  const excenv_props_t* props;
-  const excenv_control_t* control;  // nullptr when n_control == 0
-  double obs_stepsize, env_tau;     // the solver's step and the environment's tau (PMSM's dead-time advance)
-  const void* const* state_in;      // S pointers
-  const excenv_policy_t* policy;
-  void* obs_traj;                   // [N + 1][O + n_control][B]
-  void* const* state_traj;          // S pointers to [N + 1][B], or nullptr
-  void* const* last_state;          // S pointers to [B]
-  void* actions_out;                // [K][A][B] or nullptr
-  void* stream;                     // hipStream_t
-};
+// The validated call (closed_loop_call.hpp) with the MLP policy record (include/excenv.h excenv_policy_t)
+using PolicyCall = ClosedLoopCall<excenv_policy_t>;
 
 // sim_policy_kernel<M, T, SOLVER> exists for the seven models (the saturated PMSM included), the three solvers and both element
 // types, one environment per lane: the only form, so excenv_launch_opts_t.envs_per_lane must be 0 (auto) or 1.
@@ -74,12 +57,7 @@ inline int policy_refusal(const excenv_policy_t* p, int OW, int A, char* msg, si
     std::snprintf(msg, n, "%s: policy->activation must be EXCENV_ACT_RELU (0) or EXCENV_ACT_TANH (1) (got %d)", fn, p->activation);
     return EXCENV_EINVAL;
   }
-  if (!(p->clip_lo <= p->clip_hi)) {
-    std::snprintf(msg, n, "%s: policy->clip_lo = %g and policy->clip_hi = %g are not an interval (-inf / +inf: no clamp)", fn, p->clip_lo,
-                  p->clip_hi);
-    return EXCENV_EINVAL;
-  }
-  return EXCENV_OK;
+  return clip_refusal(fn, p->clip_lo, p->clip_hi, msg, n);
 }
 
 }  // namespace excenv

@@ -1,20 +1,13 @@
 """Closed-loop trajectories: `vmap_sim_ahead_feedback` runs a whole horizon in ONE persistent launch of sim_feedback_kernel through
 `excenv_sim_feedback` (include/excenv.h), with every action computed inside the kernel from the observation row it has just saved:
 affine output feedback, optional integral action, optional feedforward row. Mixed into `CoreEnvironment`
-(core_env.py).
-
-The rows are the post-processed states `vmap_step` carries ("step" semantics), so the returned observations, states and last state are
-bit for bit what `vmap_sim_ahead` returns under `sim_ahead_semantics = "step"` for the returned actions. Nothing here records a graph:
-the reverse mode through the policy is _feedback_vjp.py's, asked for with `differentiable=True`."""
+(core_env.py); what it shares with `vmap_sim_ahead_policy` is _closed_loop.py's. Nothing here records a graph: the reverse mode
+through the policy is _feedback_vjp.py's, asked for with `differentiable=True`."""
 from __future__ import annotations
-
-import ctypes
-import math
 
 import torch
 
-from . import _native
-from ._trajectory import _lane_major_leaves, _lane_major_obs
+from . import _closed_loop, _native
 
 
 class FeedbackMixin:
@@ -66,12 +59,7 @@ class FeedbackMixin:
         `vmap_generate_rew_trunc_term_ahead(states, actions)` under `env.differentiable` reaches `gain.grad`. With no input that
         requires grad the plain path runs. Refused then: `store_state_trajectory = False`, static parameters that require grad, the
         saturated PMSM, per-environment properties, graph capture."""
-        if self.traj_layout != "lane_major":
-            raise ValueError(f"vmap_sim_ahead_feedback: traj_layout={self.traj_layout!r}: the closed-loop kernel writes the "
-                             "'lane_major' layout only")
-        if self.sim_ahead_semantics == "ahead_accumulated_t":
-            raise ValueError("vmap_sim_ahead_feedback: sim_ahead_semantics='ahead_accumulated_t': a closed loop reads the saved row "
-                             "of every action, its trajectory is a chain of steps ('step' semantics) on every setting")
+        _closed_loop.refuse_settings(self, "vmap_sim_ahead_feedback", "closed-loop")
         tensors = [gain, integral_gain, feedforward, integrator_state]
         tensors += [getattr(init_state.physical_state, n) for n in self.STATE_FIELDS]
         wants = torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in tensors)
@@ -89,27 +77,11 @@ class FeedbackMixin:
     def _feedback_launch(self, init_state, gain, n_actions, obs_stepsize, action_stepsize, feedforward, integral_gain,
                          integrator_state, clip):
         """The one excenv_sim_feedback launch behind vmap_sim_ahead_feedback (its arguments, its return value); records no graph."""
-        B, S, A, OW = self.batch_size, self.physical_state_dim, self.action_dim, self._obs_dim()
-        dt, dev = self.dtype, self.device
-        assert obs_stepsize <= action_stepsize, "The action stepsize should be greater or equal to the observation stepsize."
-        phys_shape = self._phys_shape(init_state.physical_state)
-        assert phys_shape == (B, S), (
-            "The initial physical state needs to be of shape (batch_size, physical_state_dim,) which is "
-            + f"{(B, S)}, but {phys_shape} is given")
-        if feedforward is not None:
-            feedforward = torch.as_tensor(feedforward).detach()
-            assert feedforward.ndim == 3 and feedforward.shape[0] == B and feedforward.shape[2] == A, (
-                "The feedforward needs to have three dimensions: (batch_size, n_actions, action_dim) which is "
-                + f"{(B, n_actions, A)}, but {tuple(feedforward.shape)} is given")
-            assert n_actions is None or int(n_actions) == feedforward.shape[1], (
-                f"n_actions is {n_actions}, but the feedforward has {feedforward.shape[1]} action rows")
-            n_actions = feedforward.shape[1]
-        assert n_actions is not None and int(n_actions) >= 0, "n_actions is needed where no feedforward gives it"
-        K = int(n_actions)
+        B, A, OW = self.batch_size, self.action_dim, self._obs_dim()
+        _closed_loop.check_state(self, init_state, obs_stepsize, action_stepsize)
+        feedforward, K = _closed_loop.action_rows(self, feedforward, "feedforward", n_actions)
         sub = self._n_substeps(K, obs_stepsize, action_stepsize)
-        N = K * sub
-        lo, hi = (-math.inf, math.inf) if clip is None else (float(clip[0]), float(clip[1]))
-        assert lo <= hi, f"clip needs to be (low, high) with low <= high, but {clip} is given"
+        lo, hi = _closed_loop.clip_bounds(clip)
         g, Bg = self._lane_major_gain(gain, "The gain")
         gi = None
         if integral_gain is not None:
@@ -125,35 +97,12 @@ class FeedbackMixin:
             z_in = torch.as_tensor(integrator_state).detach()
             assert tuple(z_in.shape) == (B, A), (
                 f"The integrator state needs to be of shape (batch_size, action_dim) which is {(B, A)}, but {tuple(z_in.shape)} is given")
-            z_in = z_in.to(device=dev, dtype=dt).t().contiguous()  # [A][B]
-        if feedforward is not None:
-            if feedforward.device != dev or feedforward.dtype != dt:
-                feedforward = feedforward.to(device=dev, dtype=dt)
-            if K > 0 and B > 0 and tuple(feedforward.stride()) != (1, A * B, B):
-                lane_major = self.new_actions_buffer(K)
-                lane_major.copy_(feedforward)
-                feedforward = lane_major
-
-        props, _keep = self._props_for(self.env_properties, B)
-        st_in = [self._t(getattr(init_state.physical_state, n), (B,)).detach() for n in self.STATE_FIELDS]
-        control, _refs = self._control(init_state, (B,))
-        new = lambda *shape: torch.empty(shape, dtype=dt, device=dev)
-        obs_buf = new(N + 1, OW, B)
-        st_buf = [new(N + 1, B) for _ in range(S)] if self.store_state_trajectory else None
-        last = [new(B) for _ in range(S)]
-        act_buf = new(K, A, B)
-        z_buf = new(A, B) if gi is not None else None
+            z_in = z_in.to(device=self.device, dtype=self.dtype).t().contiguous()  # [A][B]
+        feedforward = _closed_loop.lane_major_rows(self, feedforward, K)
+        z_buf = torch.empty((A, B), dtype=self.dtype, device=self.device) if gi is not None else None
         policy = _native.Feedback(g.data_ptr(), _native._ptr(gi), Bg, _native._ptr(feedforward) if K > 0 else None,
                                   _native._ptr(z_in), _native._ptr(z_buf), lo, hi)
-        if B > 0:  # (an empty batch has no addresses to hand over)
-            _native._launch("excenv_sim_feedback", obs_buf, "vmap_sim_ahead_feedback", self.ENV_ID, self._solver.id,
-                            _native.dtype_id(dt), B, K, sub, ctypes.byref(props), _native._ref(control), float(obs_stepsize),
-                            float(self.tau), _native._ptrs(st_in), ctypes.byref(policy), obs_buf.data_ptr(), _native._ptrs(st_buf),
-                            _native._ptrs(last), act_buf.data_ptr() if K > 0 else None, _native._ref(self.launch_opts))
-            self.last_feedback_launch = _native.last_launch()
-        observations = _lane_major_obs(obs_buf, B, N + 1, OW)
-        states = None
-        if st_buf is not None:
-            states = self._traj_state(init_state, [_lane_major_leaves(b, 1, B, N + 1)[0] for b in st_buf], (B,), N)
-        last_state = self.State(self.PhysicalState(*last), init_state.PRNGKey, self._additions((B,), True), init_state.reference)
-        return observations, states, last_state, act_buf.permute(2, 0, 1), (z_buf.t() if z_buf is not None else None)
+        out, name = _closed_loop.launch(self, "excenv_sim_feedback", policy, "vmap_sim_ahead_feedback", init_state, K, sub, obs_stepsize)
+        if name is not None:
+            self.last_feedback_launch = name
+        return (*out, (z_buf.t() if z_buf is not None else None))

@@ -1,20 +1,16 @@
 """Policy rollouts: `vmap_sim_ahead_policy` runs a whole horizon in ONE persistent launch of sim_policy_kernel through
 `excenv_sim_policy` (include/excenv.h), with every action computed inside the kernel by a small multi-layer perceptron on the
 observation row it has just saved, plus an optional pre-sampled exploration row, clamped. Mixed into
-`CoreEnvironment` (core_env.py); `MLPPolicy` is the parameter record.
-
-The rows are the post-processed states `vmap_step` carries ("step" semantics), so the returned observations, states and last state are
-bit for bit what `vmap_sim_ahead` returns under `sim_ahead_semantics = "step"` for the returned actions. Nothing here records a graph:
-a training loop recomputes log-probabilities from the returned observation rows and actions with torch's own autograd."""
+`CoreEnvironment` (core_env.py); `MLPPolicy` is the parameter record; what the call shares with `vmap_sim_ahead_feedback`
+is _closed_loop.py's. Nothing here records a graph: a training loop recomputes log-probabilities from the returned observation
+rows and actions with torch's own autograd."""
 from __future__ import annotations
 
 import ctypes
-import math
 
 import torch
 
-from . import _native
-from ._trajectory import _lane_major_leaves, _lane_major_obs
+from . import _closed_loop, _native
 
 
 class MLPPolicy:
@@ -132,11 +128,7 @@ class PolicyMixin:
         Refused by name (ValueError): trajectory layouts other than "lane_major", `sim_ahead_semantics == "ahead_accumulated_t"`,
         and `env.differentiable` with an input or parameter that requires grad (there is no reverse mode through this launch)."""
         fn = "vmap_sim_ahead_policy"
-        if self.traj_layout != "lane_major":
-            raise ValueError(f"{fn}: traj_layout={self.traj_layout!r}: the policy kernel writes the 'lane_major' layout only")
-        if self.sim_ahead_semantics == "ahead_accumulated_t":
-            raise ValueError(f"{fn}: sim_ahead_semantics='ahead_accumulated_t': a closed loop reads the saved row of every action, "
-                             "its trajectory is a chain of steps ('step' semantics) on every setting")
+        _closed_loop.refuse_settings(self, fn, "policy")
         assert isinstance(policy, MLPPolicy), f"policy needs to be an MLPPolicy, but {type(policy).__name__} is given"
         tensors = [policy.params, noise] + [getattr(init_state.physical_state, n) for n in self.STATE_FIELDS]
         wants = any(isinstance(t, torch.Tensor) and t.requires_grad for t in tensors)
@@ -144,58 +136,19 @@ class PolicyMixin:
             raise ValueError(f"{fn}: env.differentiable with an input that requires grad: there is no reverse mode through the policy "
                              "launch; detach the inputs or set env.differentiable = False, and recompute the log-probabilities from "
                              "the returned observations and actions in torch")
-        B, S, A, OW = self.batch_size, self.physical_state_dim, self.action_dim, self._obs_dim()
-        dt, dev = self.dtype, self.device
-        assert obs_stepsize <= action_stepsize, "The action stepsize should be greater or equal to the observation stepsize."
-        phys_shape = self._phys_shape(init_state.physical_state)
-        assert phys_shape == (B, S), (
-            "The initial physical state needs to be of shape (batch_size, physical_state_dim,) which is "
-            + f"{(B, S)}, but {phys_shape} is given")
+        A, OW = self.action_dim, self._obs_dim()
+        _closed_loop.check_state(self, init_state, obs_stepsize, action_stepsize)
         assert policy.widths[0] == OW and policy.widths[-1] == A, (
             f"The policy needs to map the observation width {OW} to the action width {A}, but its widths are {policy.widths}")
-        if noise is not None:
-            noise = torch.as_tensor(noise).detach()
-            assert noise.ndim == 3 and noise.shape[0] == B and noise.shape[2] == A, (
-                "The noise needs to have three dimensions: (batch_size, n_actions, action_dim) which is "
-                + f"{(B, n_actions, A)}, but {tuple(noise.shape)} is given")
-            assert n_actions is None or int(n_actions) == noise.shape[1], (
-                f"n_actions is {n_actions}, but the noise has {noise.shape[1]} action rows")
-            n_actions = noise.shape[1]
-        assert n_actions is not None and int(n_actions) >= 0, "n_actions is needed where no noise gives it"
-        K = int(n_actions)
+        noise, K = _closed_loop.action_rows(self, noise, "noise", n_actions)
         sub = self._n_substeps(K, obs_stepsize, action_stepsize)
-        N = K * sub
-        lo, hi = (-math.inf, math.inf) if clip is None else (float(clip[0]), float(clip[1]))
-        assert lo <= hi, f"clip needs to be (low, high) with low <= high, but {clip} is given"
-        if noise is not None:
-            if noise.device != dev or noise.dtype != dt:
-                noise = noise.to(device=dev, dtype=dt)
-            if K > 0 and B > 0 and tuple(noise.stride()) != (1, A * B, B):
-                lane_major = self.new_actions_buffer(K)
-                lane_major.copy_(noise)
-                noise = lane_major
-        params = policy.on(dev, dt)
-
-        props, _keep = self._props_for(self.env_properties, B)
-        st_in = [self._t(getattr(init_state.physical_state, n), (B,)).detach() for n in self.STATE_FIELDS]
-        control, _refs = self._control(init_state, (B,))
-        new = lambda *shape: torch.empty(shape, dtype=dt, device=dev)
-        obs_buf = new(N + 1, OW, B)
-        st_buf = [new(N + 1, B) for _ in range(S)] if self.store_state_trajectory else None
-        last = [new(B) for _ in range(S)]
-        act_buf = new(K, A, B)
+        lo, hi = _closed_loop.clip_bounds(clip)
+        noise = _closed_loop.lane_major_rows(self, noise, K)
+        params = policy.on(self.device, self.dtype)
         widths = (ctypes.c_int32 * (_native.POLICY_MAX_LAYERS + 1))(*policy.widths)
         record = _native.Policy(params.data_ptr(), policy.n_layers, _native.ACTIVATIONS[policy.activation], widths,
                                 _native._ptr(noise) if K > 0 else None, lo, hi)
-        if B > 0:  # (an empty batch has no addresses to hand over)
-            _native._launch("excenv_sim_policy", obs_buf, fn, self.ENV_ID, self._solver.id, _native.dtype_id(dt), B, K, sub,
-                            ctypes.byref(props), _native._ref(control), float(obs_stepsize), float(self.tau), _native._ptrs(st_in),
-                            ctypes.byref(record), obs_buf.data_ptr(), _native._ptrs(st_buf), _native._ptrs(last),
-                            act_buf.data_ptr() if K > 0 else None, _native._ref(self.launch_opts))
-            self.last_policy_launch = _native.last_launch()
-        observations = _lane_major_obs(obs_buf, B, N + 1, OW)
-        states = None
-        if st_buf is not None:
-            states = self._traj_state(init_state, [_lane_major_leaves(b, 1, B, N + 1)[0] for b in st_buf], (B,), N)
-        last_state = self.State(self.PhysicalState(*last), init_state.PRNGKey, self._additions((B,), True), init_state.reference)
-        return observations, states, last_state, act_buf.permute(2, 0, 1)
+        out, name = _closed_loop.launch(self, "excenv_sim_policy", record, fn, init_state, K, sub, obs_stepsize)
+        if name is not None:
+            self.last_policy_launch = name
+        return out
