@@ -64,10 +64,12 @@ __device__ __forceinline__ double rng_uniform(Key key, uint32_t i, double lo, do
   return (v > lo) ? v : lo;
 }
 
-// jax.random.randint(key, (1,), lo, hi)[0], int32 form (two 32-bit draws, uint32 wrap-around arithmetic)
+// jax.random.randint(key, (1,), lo, hi)[0], int32 form (two 32-bit draws, uint32 wrap-around arithmetic). The span is the
+// difference of the bounds taken as uint32 (as _randint converts them before it subtracts): defined for every pair, where the
+// signed `hi - lo` overflows once the difference leaves int32; lo + off < hi then still fits.
 __device__ __forceinline__ int64_t rng_randint(Key key, int32_t lo, int32_t hi) {
   const uint32_t higher = rng_bits32(rng_split(key, 0), 0), lower = rng_bits32(rng_split(key, 1), 0);
-  uint32_t span = (uint32_t)(hi - lo);
+  uint32_t span = (uint32_t)hi - (uint32_t)lo;
   if (hi <= lo) span = 1u;
   uint32_t mult = 65536u % span;
   mult = (mult * mult) % span;
