@@ -772,6 +772,33 @@ int excenv_sim_policy(int env, int solver, int dtype, int64_t B, int64_t K, int3
   return t->sim_policy(pc);
 }
 
+int excenv_sim_policy_episodes(int env, int solver, int dtype, int64_t B, int64_t K, int32_t substeps, const excenv_props_t* props,
+                               const excenv_control_t* control, double obs_stepsize, double env_tau, const void* const* state_in,
+                               const excenv_policy_t* policy, void* obs_traj, void* const* state_traj, void* const* last_state,
+                               void* actions_out, const excenv_episode_t* episode, const excenv_launch_opts_t* opts, void* stream) {
+  const char* fn = "excenv_sim_policy_episodes";
+  if (int rc = check_closed_loop_head(fn, env, solver, dtype, B, K, substeps)) return rc;
+  if (int rc = check_rollout_pointers(fn, props, state_in, obs_traj, last_state)) return rc;
+  if (int rc = check_control(fn, env, control)) return rc;  // (before the policy: its first width is O + n_control)
+  const EnvVTable* d = table_public(env);
+  {
+    char why[256];
+    if (int rc = policy_refusal(policy, d->O + (control ? control->n_control : 0), d->A, why, sizeof(why), fn)) { set_error("%s", why); return rc; }
+  }
+  if (int rc = check_closed_loop_tail(fn, env, substeps, opts)) return rc;
+  {
+    char why[256];
+    if (int rc = episode_refusal(episode, d->S, substeps, why, sizeof(why))) { set_error("%s", why); return rc; }
+  }
+  int trc;
+  const EnvVTable* t = table_for(env, props, &trc);
+  if (!t) return trc;
+  const EpisodeCall ec{{solver, dtype, B, K, substeps, props, control, obs_stepsize, env_tau, state_in, policy, obs_traj, state_traj,
+                        last_state, actions_out, stream},
+                       episode};
+  return t->sim_policy_episodes(ec);
+}
+
 int excenv_state_from_observation(int env, int dtype, int64_t B, const excenv_props_t* props, int32_t n_control,
                                   const int32_t* control_idx, const void* obs, void* const* state_out,
                                   void* const* reference_out, void* stream) {

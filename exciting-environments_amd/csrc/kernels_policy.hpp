@@ -265,9 +265,8 @@ sim_policy_kernel(const PolicyArgs<T, M> ka, const T* __restrict__ params) {
   }
 }
 
-// Packs PolicyArgs and launches the instantiation of the call's solver
-template <class M, typename T> static int launch_policy(const PolicyCall& pc) {
-  PolicyArgs<T, M> ka;
+// Packs PolicyArgs from a validated call, under the entry point's name `fn`; `blocks`: the workgroups of its launch
+template <class M, typename T> static int pack_policy_args(const char* fn, const PolicyCall& pc, PolicyArgs<T, M>& ka, int64_t* blocks) {
   std::memset(&ka, 0, sizeof(ka));
   fill_props<T, M>(ka.kp, pc.props);
   double coef;
@@ -277,8 +276,8 @@ template <class M, typename T> static int launch_policy(const PolicyCall& pc) {
   ka.substeps = pc.substeps;
   ka.n_control = pc.control ? pc.control->n_control : 0;
   for (int j = 0; j < M::S; ++j) {
-    if (!pc.state_in[j] || !pc.last_state[j]) { set_error("excenv_sim_policy: state pointer %d is NULL", j); return EXCENV_ENULL; }
-    if (pc.state_traj && !pc.state_traj[j]) { set_error("excenv_sim_policy: state_traj pointer %d is NULL", j); return EXCENV_ENULL; }
+    if (!pc.state_in[j] || !pc.last_state[j]) { set_error("%s: state pointer %d is NULL", fn, j); return EXCENV_ENULL; }
+    if (pc.state_traj && !pc.state_traj[j]) { set_error("%s: state_traj pointer %d is NULL", fn, j); return EXCENV_ENULL; }
     ka.state_in[j] = (const T*)pc.state_in[j];
     ka.last_state[j] = (T*)pc.last_state[j];
     ka.straj[j] = pc.state_traj ? (T*)pc.state_traj[j] : nullptr;
@@ -300,12 +299,21 @@ template <class M, typename T> static int launch_policy(const PolicyCall& pc) {
   ka.dt = (T)pc.obs_stepsize;
   ka.env_tau = (T)pc.env_tau;
   ka.adv_coef = (T)coef;
-  if (pc.B == 0) return EXCENV_OK;
-  const int64_t blocks = (pc.B + POLICY_BLOCK - 1) / POLICY_BLOCK;
-  if (blocks > (int64_t)0x7fffffff) {
-    set_error("excenv_sim_policy: ceil(B / %d) = %lld workgroups exceed one launch", POLICY_BLOCK, (long long)blocks);
+  *blocks = (pc.B + POLICY_BLOCK - 1) / POLICY_BLOCK;
+  if (*blocks > (int64_t)0x7fffffff) {
+    set_error("%s: ceil(B / %d) = %lld workgroups exceed one launch", fn, POLICY_BLOCK, (long long)*blocks);
     return EXCENV_EINVAL;
   }
+  return EXCENV_OK;
+}
+
+// Launches the instantiation of the call's solver
+template <class M, typename T> static int launch_policy(const PolicyCall& pc) {
+  PolicyArgs<T, M> ka;
+  int64_t blocks;
+  if (int rc = pack_policy_args<M, T>("excenv_sim_policy", pc, ka, &blocks)) return rc;
+  const excenv_policy_t& p = *pc.policy;
+  if (pc.B == 0) return EXCENV_OK;
   const dim3 grid((unsigned)blocks), block(POLICY_BLOCK);
   const size_t lds = policy_lds_bytes(p, sizeof(T));
   const hipStream_t stream = (hipStream_t)pc.stream;

@@ -1,6 +1,7 @@
 // Policy rollouts: what one excenv_sim_policy call launches. Host-only and free of HIP, like feedback.hpp: the call record, what the
 // entry point refuses about the policy before any launch, the layout of the parameter array, the dynamic LDS of a launch and the
-// name of sim_policy_kernel (kernels_policy.hpp).
+// name of sim_policy_kernel (kernels_policy.hpp). Below them the same for excenv_sim_policy_episodes: the call with its episode
+// record, what the entry point refuses about that record, the name of sim_episodes_kernel (kernels_policy_episodes.hpp).
 #pragma once
 #include "closed_loop_call.hpp"
 
@@ -32,10 +33,9 @@ inline int64_t policy_param_count(const excenv_policy_t& p) {
   return n;
 }
 
-// What excenv_sim_policy refuses about the policy record for an environment of observation width OW and A actions: EXCENV_OK, or
+// What excenv_sim_policy (and excenv_sim_policy_episodes, under its own name `fn`) refuses about the policy record for an environment of observation width OW and A actions: EXCENV_OK, or
 // the code with the message in `msg`. NULL pointers first, then values. A NaN bound fails `lo <= hi`.
-inline int policy_refusal(const excenv_policy_t* p, int OW, int A, char* msg, size_t n) {
-  const char* fn = "excenv_sim_policy";
+inline int policy_refusal(const excenv_policy_t* p, int OW, int A, char* msg, size_t n, const char* fn = "excenv_sim_policy") {
   if (!p) { std::snprintf(msg, n, "%s: policy is NULL", fn); return EXCENV_ENULL; }
   if (!p->params) { std::snprintf(msg, n, "%s: policy->params is NULL", fn); return EXCENV_ENULL; }
   if (p->n_layers < 1 || p->n_layers > EXCENV_POLICY_MAX_LAYERS) {
@@ -58,6 +58,48 @@ inline int policy_refusal(const excenv_policy_t* p, int OW, int A, char* msg, si
     return EXCENV_EINVAL;
   }
   return clip_refusal(fn, p->clip_lo, p->clip_hi, msg, n);
+}
+
+// ---- episode rollouts: excenv_sim_policy_episodes ------------------------------------------------------------------
+// The validated call: a policy call with the episode record (include/excenv.h excenv_episode_t)
+struct EpisodeCall {
+  PolicyCall call;
+  const excenv_episode_t* episode;
+};
+
+// sim_episodes_kernel<M, T, SOLVER> (kernels_policy_episodes.hpp): the same 42 instantiations, one environment per lane
+constexpr const char* episodes_name() { return "sim_episodes_kernel"; }
+
+// What excenv_sim_policy_episodes refuses about the episode record of a model with S state fields, behind every check of
+// excenv_sim_policy: EXCENV_OK, or the code with the message in `msg`. NULL pointers first, then values.
+inline int episode_refusal(const excenv_episode_t* e, int S, int32_t substeps, char* msg, size_t n) {
+  const char* fn = "excenv_sim_policy_episodes";
+  if (!e) { std::snprintf(msg, n, "%s: episode is NULL", fn); return EXCENV_ENULL; }
+  if (!e->reset_states) { std::snprintf(msg, n, "%s: episode->reset_states is NULL", fn); return EXCENV_ENULL; }
+  for (int j = 0; j < S; ++j)
+    if (!e->reset_states[j]) { std::snprintf(msg, n, "%s: episode->reset_states pointer %d is NULL", fn, j); return EXCENV_ENULL; }
+  if (substeps != 1) {
+    std::snprintf(msg, n, "%s: substeps must be 1 (one solver step per action, as GymWrapper.step does; got %d)", fn, substeps);
+    return EXCENV_EINVAL;
+  }
+  if (e->n_reset_rows < 1) {
+    std::snprintf(msg, n, "%s: episode->n_reset_rows must be at least 1 (got %d)", fn, e->n_reset_rows);
+    return EXCENV_EINVAL;
+  }
+  if (e->end_mask & ~(EXCENV_END_TERMINATED | EXCENV_END_TRUNCATED)) {
+    std::snprintf(msg, n, "%s: episode->end_mask has unknown bits (got %d; EXCENV_END_TERMINATED = 1, EXCENV_END_TRUNCATED = 2)", fn,
+                  e->end_mask);
+    return EXCENV_EINVAL;
+  }
+  if (e->max_episode_steps < 0) {
+    std::snprintf(msg, n, "%s: episode->max_episode_steps must not be negative (got %d; 0: no time limit)", fn, e->max_episode_steps);
+    return EXCENV_EINVAL;
+  }
+  if (e->end_mask == 0 && e->max_episode_steps == 0) {
+    std::snprintf(msg, n, "%s: episode->end_mask = 0 and episode->max_episode_steps = 0: nothing can end an episode (use excenv_sim_policy)", fn);
+    return EXCENV_EINVAL;
+  }
+  return EXCENV_OK;
 }
 
 }  // namespace excenv

@@ -1,0 +1,4 @@
+// Episode rollout kernel instantiations for one environment (its own translation unit so the six compile in parallel).
+#include "kernels_policy_episodes.hpp"
+template int excenv::policy_episodes_entry<excenv::Pmsm>(const excenv::EpisodeCall&);
+template int excenv::policy_episodes_entry<excenv::PmsmSat>(const excenv::EpisodeCall&);  // the saturated model: tables in global memory

@@ -71,10 +71,11 @@ def clip_bounds(clip):
     return lo, hi
 
 
-def launch(env, entry, record, caller, init_state, K, sub, obs_stepsize):
-    """One `entry` launch (excenv_sim_feedback or excenv_sim_policy) with the ctypes policy `record`, for `caller` ->
-    ((observations [B, N+1, OW], states with leaves [B, N+1] or None, last_state with leaves [B], actions [B, K, A]),
-    excenv_last_launch() of it or None for an empty batch). Views of freshly allocated lane-major memory."""
+def launch(env, entry, record, caller, init_state, K, sub, obs_stepsize, extra=()):
+    """One `entry` launch (excenv_sim_feedback, excenv_sim_policy or excenv_sim_policy_episodes) with the ctypes policy `record`, for
+    `caller` -> ((observations [B, N+1, OW], states with leaves [B, N+1] or None, last_state with leaves [B], actions [B, K, A]),
+    excenv_last_launch() of it or None for an empty batch). Views of freshly allocated lane-major memory. extra: the C arguments
+    an entry has between `actions_out` and `opts` (the episode record)."""
     B, S, A, OW = env.batch_size, env.physical_state_dim, env.action_dim, env._obs_dim()
     dt, N = env.dtype, K * sub
     props, _keep = env._props_for(env.env_properties, B)
@@ -90,7 +91,7 @@ def launch(env, entry, record, caller, init_state, K, sub, obs_stepsize):
         _native._launch(entry, obs_buf, caller, env.ENV_ID, env._solver.id, _native.dtype_id(dt), B, K, sub, ctypes.byref(props),
                         _native._ref(control), float(obs_stepsize), float(env.tau), _native._ptrs(st_in), ctypes.byref(record),
                         obs_buf.data_ptr(), _native._ptrs(st_buf), _native._ptrs(last), act_buf.data_ptr() if K > 0 else None,
-                        _native._ref(env.launch_opts))
+                        *extra, _native._ref(env.launch_opts))
         name = _native.last_launch()
     observations = _lane_major_obs(obs_buf, B, N + 1, OW)
     states = None

@@ -33,6 +33,8 @@ ABI_VERSION = 7
 POLICY_MAX_LAYERS, POLICY_MAX_WIDTH = 4, 64  # excenv_policy_t: linear layers of the MLP, units of a hidden layer
 ACT_RELU, ACT_TANH = 0, 1
 ACTIVATIONS = {"relu": ACT_RELU, "tanh": ACT_TANH}
+END_TERMINATED, END_TRUNCATED = 1, 2  # excenv_episode_t.end_mask
+END_ON = {"terminated": END_TERMINATED, "truncated": END_TRUNCATED}
 
 _LIB_PATH = os.environ.get(  # EXCENV_HIP_LIB: A/B-test another build of the same library (tuning experiments)
     "EXCENV_HIP_LIB", os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libexcenv_hip.so"))
@@ -109,10 +111,19 @@ class Policy(ctypes.Structure):
                 ("clip_hi", ctypes.c_double)]
 
 
+class Episode(ctypes.Structure):
+    """excenv_episode_t: the reset rows, the end conditions and the gym / reset outputs of excenv_sim_policy_episodes."""
+
+    _fields_ = [("reset_states", ctypes.c_void_p), ("n_reset_rows", ctypes.c_int32), ("end_mask", ctypes.c_int32),
+                ("max_episode_steps", ctypes.c_int32), ("episode_steps_in", ctypes.c_void_p), ("reward", ctypes.c_void_p),
+                ("terminated", ctypes.c_void_p), ("truncated", ctypes.c_void_p), ("reset", ctypes.c_void_p),
+                ("n_resets", ctypes.c_void_p), ("episode_steps_out", ctypes.c_void_p)]
+
+
 # the C types of the header's structures (tests/test_native_binding.py compares sizes and field offsets with the host compiler's)
 STRUCTS = {Param: "excenv_param_t", PmsmLut: "excenv_pmsm_lut_t", Props: "excenv_props_t", LaunchOpts: "excenv_launch_opts_t",
            TrajGym: "excenv_traj_gym_t", Control: "excenv_control_t", Feedback: "excenv_feedback_t",
-           FeedbackVjp: "excenv_feedback_vjp_t", Policy: "excenv_policy_t"}
+           FeedbackVjp: "excenv_feedback_vjp_t", Policy: "excenv_policy_t", Episode: "excenv_episode_t"}
 
 _vp, _ci, _i32, _i64, _cd = ctypes.c_void_p, ctypes.c_int, ctypes.c_int32, ctypes.c_int64, ctypes.c_double
 _STEP = [_ci, _ci, _ci, _i64, _vp, _vp, _cd, _vp, _vp, _vp, _vp]  # env, solver, dtype, B, props, control, tau, in, action, out, obs
@@ -165,6 +176,9 @@ PROTOTYPES = {
     "excenv_sim_feedback": (_ci, [_ci, _ci, _ci, _i64, _i64, _i32, _vp, _vp, _cd, _cd, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     # the arguments of excenv_sim_feedback, `policy` an excenv_policy_t
     "excenv_sim_policy": (_ci, [_ci, _ci, _ci, _i64, _i64, _i32, _vp, _vp, _cd, _cd, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # the arguments of excenv_sim_policy with `episode` (an excenv_episode_t) behind actions_out
+    "excenv_sim_policy_episodes": (_ci, [_ci, _ci, _ci, _i64, _i64, _i32, _vp, _vp, _cd, _cd, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                         _vp]),
     "excenv_sim_feedback_vjp_workspace_bytes": (_i64, [_ci, _ci, _i64, _i64, _i32, _i64, _ci]),
     "excenv_sim_feedback_vjp_bytes": (_i64, [_ci, _ci, _i32, _i32, _ci, _ci, _ci, _ci]),
     # env, solver, dtype, B, K, substeps, props, control, obs_stepsize, env_tau, call, workspace, workspace_bytes, opts, stream

@@ -2,10 +2,12 @@
 `excenv_sim_policy` (include/excenv.h), with every action computed inside the kernel by a small multi-layer perceptron on the
 observation row it has just saved, plus an optional pre-sampled exploration row, clamped. Mixed into
 `CoreEnvironment` (core_env.py); `MLPPolicy` is the parameter record; what the call shares with `vmap_sim_ahead_feedback`
-is _closed_loop.py's. Nothing here records a graph: a training loop recomputes log-probabilities from the returned observation
+is _closed_loop.py's. `vmap_rollout_episodes` is the same rollout with rewards, flags, a step budget and resets inside the launch
+(sim_episodes_kernel through `excenv_sim_policy_episodes`). Nothing here records a graph: a training loop recomputes log-probabilities from the returned observation
 rows and actions with torch's own autograd."""
 from __future__ import annotations
 
+import collections
 import ctypes
 
 import torch
@@ -105,9 +107,37 @@ class MLPPolicy:
         return cls([m.weight for m in linears], [m.bias for m in linears], activation, device=device, dtype=dtype)
 
 
+# what `vmap_rollout_episodes` returns: zero-copy views of lane-major memory (`states` is None without a state trajectory)
+EpisodeRollout = collections.namedtuple(
+    "EpisodeRollout", "observations states last_state actions reward truncated terminated reset n_resets episode_steps")
+
+
 class PolicyMixin:
-    # excenv_last_launch() of the most recent excenv_sim_policy launch of this environment
+    # excenv_last_launch() of the most recent excenv_sim_policy / excenv_sim_policy_episodes launch of this environment
     last_policy_launch = ""
+
+    def _policy_call(self, fn, init_state, policy, noise, n_actions, obs_stepsize, action_stepsize, clip):
+        """The checks and the excenv_policy_t record both policy launches share -> (record, its tensors to keep alive, K, substeps)"""
+        assert isinstance(policy, MLPPolicy), f"policy needs to be an MLPPolicy, but {type(policy).__name__} is given"
+        tensors = [policy.params, noise] + [getattr(init_state.physical_state, n) for n in self.STATE_FIELDS]
+        wants = any(isinstance(t, torch.Tensor) and t.requires_grad for t in tensors)
+        if self.differentiable and torch.is_grad_enabled() and (self._param_leaves() or wants):
+            raise ValueError(f"{fn}: env.differentiable with an input that requires grad: there is no reverse mode through the policy "
+                             "launch; detach the inputs or set env.differentiable = False, and recompute the log-probabilities from "
+                             "the returned observations and actions in torch")
+        A, OW = self.action_dim, self._obs_dim()
+        _closed_loop.check_state(self, init_state, obs_stepsize, action_stepsize)
+        assert policy.widths[0] == OW and policy.widths[-1] == A, (
+            f"The policy needs to map the observation width {OW} to the action width {A}, but its widths are {policy.widths}")
+        noise, K = _closed_loop.action_rows(self, noise, "noise", n_actions)
+        sub = self._n_substeps(K, obs_stepsize, action_stepsize)
+        lo, hi = _closed_loop.clip_bounds(clip)
+        noise = _closed_loop.lane_major_rows(self, noise, K)
+        params = policy.on(self.device, self.dtype)
+        widths = (ctypes.c_int32 * (_native.POLICY_MAX_LAYERS + 1))(*policy.widths)
+        record = _native.Policy(params.data_ptr(), policy.n_layers, _native.ACTIVATIONS[policy.activation], widths,
+                                _native._ptr(noise) if K > 0 else None, lo, hi)
+        return record, (params, noise), K, sub
 
     def vmap_sim_ahead_policy(self, init_state, policy, n_actions, obs_stepsize, action_stepsize, noise=None, clip=(-1.0, 1.0)):
         """Rollouts of all batch_size environments under an MLP policy in one kernel launch -> (observations [B, N+1, OW], states
@@ -129,26 +159,86 @@ class PolicyMixin:
         and `env.differentiable` with an input or parameter that requires grad (there is no reverse mode through this launch)."""
         fn = "vmap_sim_ahead_policy"
         _closed_loop.refuse_settings(self, fn, "policy")
-        assert isinstance(policy, MLPPolicy), f"policy needs to be an MLPPolicy, but {type(policy).__name__} is given"
-        tensors = [policy.params, noise] + [getattr(init_state.physical_state, n) for n in self.STATE_FIELDS]
-        wants = any(isinstance(t, torch.Tensor) and t.requires_grad for t in tensors)
-        if self.differentiable and torch.is_grad_enabled() and (self._param_leaves() or wants):
-            raise ValueError(f"{fn}: env.differentiable with an input that requires grad: there is no reverse mode through the policy "
-                             "launch; detach the inputs or set env.differentiable = False, and recompute the log-probabilities from "
-                             "the returned observations and actions in torch")
-        A, OW = self.action_dim, self._obs_dim()
-        _closed_loop.check_state(self, init_state, obs_stepsize, action_stepsize)
-        assert policy.widths[0] == OW and policy.widths[-1] == A, (
-            f"The policy needs to map the observation width {OW} to the action width {A}, but its widths are {policy.widths}")
-        noise, K = _closed_loop.action_rows(self, noise, "noise", n_actions)
-        sub = self._n_substeps(K, obs_stepsize, action_stepsize)
-        lo, hi = _closed_loop.clip_bounds(clip)
-        noise = _closed_loop.lane_major_rows(self, noise, K)
-        params = policy.on(self.device, self.dtype)
-        widths = (ctypes.c_int32 * (_native.POLICY_MAX_LAYERS + 1))(*policy.widths)
-        record = _native.Policy(params.data_ptr(), policy.n_layers, _native.ACTIVATIONS[policy.activation], widths,
-                                _native._ptr(noise) if K > 0 else None, lo, hi)
+        record, _keep, K, sub = self._policy_call(fn, init_state, policy, noise, n_actions, obs_stepsize, action_stepsize, clip)
         out, name = _closed_loop.launch(self, "excenv_sim_policy", record, fn, init_state, K, sub, obs_stepsize)
         if name is not None:
             self.last_policy_launch = name
         return out
+
+    def _reset_rows(self, reset_states):
+        """`reset_states` of vmap_rollout_episodes as S leaves over [R][B] memory -> (leaves, R). A `State` is one row, a list of
+        them R rows, a physical-state tree has leaves [B, R]; only what is not laid out as [R][B] already is copied."""
+        B = self.batch_size
+        if isinstance(reset_states, (list, tuple)):
+            assert len(reset_states) >= 1, "reset_states needs at least one State"
+            rows = [[self._t(getattr(s.physical_state, n), (B,)).detach() for s in reset_states] for n in self.STATE_FIELDS]
+            return [r[0][None] if len(r) == 1 else torch.stack(r) for r in rows], len(reset_states)
+        if hasattr(reset_states, "physical_state"):
+            return [self._t(getattr(reset_states.physical_state, n), (B,)).detach()[None] for n in self.STATE_FIELDS], 1
+        leaves = [torch.as_tensor(getattr(reset_states, n)).detach() for n in self.STATE_FIELDS]
+        R = leaves[0].shape[1] if leaves[0].ndim == 2 else 0
+        assert R >= 1 and all(tuple(x.shape) == (B, R) for x in leaves), (
+            "reset_states needs to be a State, a list of States or a physical state with leaves of shape (batch_size, n_reset_rows) "
+            + f"which is {(B, 'R')}, but {[tuple(x.shape) for x in leaves]} is given")
+        return [x.to(device=self.device, dtype=self.dtype).t().contiguous() for x in leaves], R
+
+    def vmap_rollout_episodes(self, init_state, policy, n_actions, stepsize, reset_states, noise=None, clip=(-1.0, 1.0),
+                              end_on=("terminated", "truncated"), max_episode_steps=0, episode_steps=None):
+        """`vmap_sim_ahead_policy` with the rewards, the flags and the episode boundaries inside the same kernel launch: K = n_actions
+        steps of `stepsize` for all batch_size environments -> EpisodeRollout(observations [B, K+1, OW], states with leaves
+        [B, K+1] (None with `env.store_state_trajectory = False`), last_state, actions [B, K, A], reward [B, K], truncated
+        [B, K+1, TW] bool, terminated [B, K] bool, reset [B, K] bool, n_resets [B] int32, episode_steps [B] int32).
+
+        Row n of an environment is judged as soon as it is saved: the episode ends there when `terminated` / `truncated` (those named
+        in `end_on`) is set for the row's state, or when the running episode already has `max_episode_steps` steps (0: no limit;
+        `episode_steps` [B] gives the steps taken before this call, None: zeros). Then reset[:, n] is True, the action of row n is
+        computed and returned but not applied, and row n + 1 is the environment's next reset state: row (e mod R) of `reset_states`
+        at its e-th reset within the call. Otherwise row n + 1 is `vmap_step`'s result, bit for bit. Row n with reset[:, n] is the
+        terminal observation and row n + 1 the first one of the next episode (gymnasium's "next-step" convention): a trainer masks the
+        transitions with reset[:, n]. Row 0 is judged like every other row; its `terminated` value has no slot, reset[:, 0] shows the
+        verdict. reward[:, n - 1] / terminated[:, n - 1] / truncated[:, n] belong to row n and are pure functions of it, reset rows
+        included: bit for bit `vmap_generate_rew_trunc_term_ahead(states, actions)`. References stay as they are along the call; a
+        reset state that is itself terminal resets again one step later.
+
+        reset_states: a `State` (from `vmap_reset` / `vmap_init_state`: R = 1), a list of them, or a physical state with leaves
+        [B, R]. Without a `control_state` the reward of every model but the PMSM is 0 and its `terminated` is `reward == 0` in every
+        row (the reference's semantics): "terminated" in `end_on` then resets on every step, `end_on=("truncated",)` is the usual
+        choice there. episode_steps of the result carries over to the next call.
+
+        Refused by name (ValueError): what `vmap_sim_ahead_policy` refuses, an unknown `end_on` entry, and `end_on=()` with
+        `max_episode_steps=0` (nothing can end an episode: that is `vmap_sim_ahead_policy`)."""
+        fn = "vmap_rollout_episodes"
+        _closed_loop.refuse_settings(self, fn, "episode")
+        mask = 0
+        for name in end_on:
+            if name not in _native.END_ON:
+                raise ValueError(f"{fn}: end_on entry {name!r}: 'terminated' or 'truncated'")
+            mask |= _native.END_ON[name]
+        max_episode_steps = int(max_episode_steps)
+        assert 0 <= max_episode_steps < 2 ** 31, f"max_episode_steps needs to be a non-negative int32, but {max_episode_steps} is given"
+        if mask == 0 and max_episode_steps == 0:
+            raise ValueError(f"{fn}: end_on=() and max_episode_steps=0: nothing can end an episode; that is vmap_sim_ahead_policy")
+        record, _keep, K, _sub = self._policy_call(fn, init_state, policy, noise, n_actions, stepsize, stepsize, clip)
+        B, dev = self.batch_size, self.device
+        rows, R = self._reset_rows(reset_states)
+        steps_in = None
+        if episode_steps is not None:
+            steps_in = torch.as_tensor(episode_steps).detach().to(device=dev, dtype=torch.int32).contiguous()
+            assert tuple(steps_in.shape) == (B,), (
+                f"episode_steps needs to be of shape (batch_size,) which is {(B,)}, but {tuple(steps_in.shape)} is given")
+        TW = _native.truncated_width(self.ENV_ID, len(self.control_state))
+        rew = torch.empty((K, B), dtype=self.dtype, device=dev)
+        term = torch.empty((K, B), dtype=torch.bool, device=dev)
+        trunc = torch.empty((K + 1, B, TW), dtype=torch.bool, device=dev)
+        reset = torch.empty((K, B), dtype=torch.bool, device=dev)
+        n_resets = torch.zeros(B, dtype=torch.int32, device=dev)
+        steps_out = torch.zeros(B, dtype=torch.int32, device=dev)
+        row_ptrs = _native._ptrs(rows)  # (alive until the launch is enqueued)
+        episode = _native.Episode(ctypes.addressof(row_ptrs), R, mask, max_episode_steps, _native._ptr(steps_in),
+                                  rew.data_ptr(), term.data_ptr(), trunc.data_ptr(), reset.data_ptr(), n_resets.data_ptr(),
+                                  steps_out.data_ptr())
+        (obs, states, last, actions), name = _closed_loop.launch(self, "excenv_sim_policy_episodes", record, fn, init_state, K, 1, stepsize,
+                                                                 extra=(ctypes.byref(episode),))
+        if name is not None:
+            self.last_policy_launch = name
+        return EpisodeRollout(obs, states, last, actions, rew.t(), trunc.permute(1, 0, 2), term.t(), reset.t(), n_resets, steps_out)

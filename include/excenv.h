@@ -519,6 +519,57 @@ int excenv_sim_policy(int env, int solver, int dtype, int64_t B, int64_t K, int3
                       const excenv_policy_t* policy, void* obs_traj, void* const* state_traj, void* const* last_state,
                       void* actions_out, const excenv_launch_opts_t* opts, void* stream);
 
+/* ---- episode rollouts: excenv_sim_policy with rewards, flags and resets INSIDE the one persistent launch of
+ * sim_episodes_kernel (an addition, same ABI version: a binder probes for the symbol). One solver step per action, as
+ * GymWrapper.step does: substeps must be 1, so N = K. Per environment, with st_0 = state_in, t_0 = episode_steps_in (0 where NULL),
+ * e = 0, R = n_reset_rows and TW = excenv_truncated_width(env, n_control):
+ *   for n = 0 .. K:
+ *     save row n: the observation row, the state row, truncated[n][:] = generate_truncated(st_n)
+ *     if n >= 1: reward[n-1] = generate_reward(st_n), terminated[n-1] = generate_terminated(st_n)
+ *     if n == K: break
+ *     a[n] = clamp(noise[n] + mlp(obs row n))          (excenv_sim_policy's contract; written to actions_out[n] in every case)
+ *     end_n = (end_mask & EXCENV_END_TERMINATED and terminated(st_n)) or (end_mask & EXCENV_END_TRUNCATED and any truncated(st_n)[:])
+ *             or (max_episode_steps > 0 and t_n >= max_episode_steps)
+ *     reset[n] = end_n
+ *     if end_n: st_{n+1} = reset_states[e mod R];  e += 1;  t_{n+1} = 0         (the action is ignored)
+ *     else:     st_{n+1} = excenv_step(st_n, a[n]);          t_{n+1} = t_n + 1  (bit for bit)
+ *   last_state = st_K;  n_resets = e;  episode_steps_out = t_K
+ * Row 0 is judged like every other row: its `terminated` value has no output slot, reset[0] shows the verdict. Every gym output is a
+ * pure function of the saved row it belongs to, reset rows included, so reward / terminated / truncated are bit for bit what
+ * excenv_rew_trunc_term gives on state_traj. A trainer masks the transitions with reset[n] == 1: row n is the terminal observation,
+ * row n + 1 the first of the next episode. References are constant along the call; a reset does not redraw them. A reset state that
+ * is itself terminal resets again on the next step. Without a control block the reward of the five non-PMSM models is 0 and their
+ * terminated flag is `reward == 0`: with EXCENV_END_TERMINATED every step is then a reset (the reference's semantics);
+ * EXCENV_END_TRUNCATED alone is the usual choice there.
+ *   reset_states      : S pointers, each lane-major [R][B]; an environment's e-th reset within the call takes row e mod R
+ *   episode_steps_in  : [B] int32 or NULL (zeros): the steps already taken in the running episode
+ *   reward            : (out) [K][B], working dtype;  terminated: (out) [K][B] bytes;  truncated: (out) [K+1][B][TW] bytes: the
+ *                       lane-major layouts of excenv_traj_gym_t;  reset: (out) [K][B] bytes;  n_resets, episode_steps_out: (out)
+ *                       [B] int32. Each output may be NULL.
+ * K == 0: row 0 and truncated[0] are written, n_resets = 0, episode_steps_out = episode_steps_in. B == 0: EXCENV_OK without a launch.
+ * excenv_last_launch() reports "sim_episodes_kernel". Validated in excenv_sim_policy's order, then this record. EXCENV_ENULL: a NULL
+ * record, NULL reset_states or a NULL leaf in it. EXCENV_EINVAL: substeps != 1, n_reset_rows < 1, unknown bits in end_mask,
+ * max_episode_steps < 0, and end_mask == 0 with max_episode_steps == 0 (nothing could end an episode: excenv_sim_policy is that). */
+#define EXCENV_END_TERMINATED 1
+#define EXCENV_END_TRUNCATED 2
+typedef struct {
+  const void* const* reset_states; /* S pointers to [n_reset_rows][B]; required */
+  int32_t n_reset_rows;            /* R >= 1 */
+  int32_t end_mask;                /* EXCENV_END_TERMINATED | EXCENV_END_TRUNCATED */
+  int32_t max_episode_steps;       /* >= 0; 0: no time limit */
+  const int32_t* episode_steps_in; /* [B] or NULL (zeros) */
+  void* reward;                    /* (out) [K][B] or NULL */
+  uint8_t* terminated;             /* (out) [K][B] or NULL */
+  uint8_t* truncated;              /* (out) [K+1][B][TW] or NULL */
+  uint8_t* reset;                  /* (out) [K][B] or NULL */
+  int32_t* n_resets;               /* (out) [B] or NULL */
+  int32_t* episode_steps_out;      /* (out) [B] or NULL */
+} excenv_episode_t;
+int excenv_sim_policy_episodes(int env, int solver, int dtype, int64_t B, int64_t K, int32_t substeps, const excenv_props_t* props,
+                               const excenv_control_t* control, double obs_stepsize, double env_tau, const void* const* state_in,
+                               const excenv_policy_t* policy, void* obs_traj, void* const* state_traj, void* const* last_state,
+                               void* actions_out, const excenv_episode_t* episode, const excenv_launch_opts_t* opts, void* stream);
+
 /* ---- reverse mode of excenv_sim_feedback: the vector-Jacobian product of one closed-loop trajectory with respect to the initial
  * state, the gains, the feedforward rows and the initial integrator state, from the rows that call saved (additions, same ABI
  * version: a binder probes for the symbols). The forward, at action row k (n = k * substeps, ob = saved observation row n with all
