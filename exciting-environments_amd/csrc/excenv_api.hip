@@ -799,6 +799,42 @@ int excenv_sim_policy_episodes(int env, int solver, int dtype, int64_t B, int64_
   return t->sim_policy_episodes(ec);
 }
 
+int64_t excenv_sim_policy_vjp_bytes(int env, int dtype, int32_t n_control, int32_t substeps, int has_grad_obs, int has_grad_states,
+                                    int has_grad_actions, int has_reset) {
+  const EnvVTable* t = table_public(env);
+  if (!t || (dtype != EXCENV_F32 && dtype != EXCENV_F64) || n_control < 0 || n_control > EXCENV_MAX_CONTROL || substeps < 1) return -1;
+  if (has_reset && substeps != 1) return -1;
+  return policy_vjp_bytes(t->S, t->A, t->O, dtype == EXCENV_F64 ? 8 : 4, n_control, substeps, has_grad_obs != 0, has_grad_states != 0,
+                          has_grad_actions != 0, has_reset != 0);
+}
+
+int excenv_sim_policy_vjp(int env, int solver, int dtype, int64_t B, int64_t K, int32_t substeps, const excenv_props_t* props,
+                          const excenv_control_t* control, double obs_stepsize, double env_tau, const excenv_policy_vjp_t* call,
+                          const excenv_launch_opts_t* opts, void* stream) {
+  const char* fn = "excenv_sim_policy_vjp";
+  if (int rc = check_closed_loop_head(fn, env, solver, dtype, B, K, substeps)) return rc;
+  if (int rc = check_reverse_props(fn, props)) return rc;
+  if (!call) { set_error("%s: call is NULL", fn); return EXCENV_ENULL; }
+  // (before the policy: its first width is O + n_control. Only the count is read — references get no gradient — so a control block
+  // that carries nothing else is valid here, as for excenv_sim_ahead_vjp)
+  if (control && control->n_control == 0) control = nullptr;
+  if (control)
+    if (int rc = check_n_control(fn, control->n_control)) return rc;
+  const EnvVTable* t = table_public(env);
+  {
+    char why[256];
+    if (int rc = policy_refusal(&call->policy, t->O + (control ? control->n_control : 0), t->A, why, sizeof(why), fn)) { set_error("%s", why); return rc; }
+  }
+  if (int rc = check_closed_loop_tail(fn, env, substeps, opts)) return rc;
+  {
+    char why[256];
+    if (int rc = policy_vjp_refusal(call, K, substeps, why, sizeof(why))) { set_error("%s", why); return rc; }
+  }
+  if (int rc = check_broadcast_props(fn, env, props)) return rc;
+  const PolicyVjpCall vc{solver, dtype, B, K, substeps, props, control, obs_stepsize, env_tau, call, stream};
+  return t->sim_policy_vjp(vc);
+}
+
 int excenv_state_from_observation(int env, int dtype, int64_t B, const excenv_props_t* props, int32_t n_control,
                                   const int32_t* control_idx, const void* obs, void* const* state_out,
                                   void* const* reference_out, void* stream) {

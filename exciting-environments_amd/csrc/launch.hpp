@@ -146,6 +146,7 @@ struct EnvVTable {
   int (*sim_feedback_vjp)(const FeedbackVjpCall&);  // reverse mode of sim_feedback (kernels_feedback_vjp.hpp)
   int (*sim_policy)(const PolicyCall&);  // sim with the actions computed by an MLP in the launch (kernels_policy.hpp)
   int (*sim_policy_episodes)(const EpisodeCall&);  // sim_policy with gym outputs and resets in the launch (kernels_policy_episodes.hpp)
+  int (*sim_policy_vjp)(const PolicyVjpCall&);  // reverse mode of sim_policy (kernels_policy_vjp.hpp)
 };
 
 // The reverse-mode entries of a model and its closed-loop entry: declared here so that they sit in the same table as every other entry
@@ -160,6 +161,7 @@ template <template <typename> class MT> int feedback_entry(const FeedbackCall&);
 template <template <typename> class MT> int feedback_vjp_entry(const FeedbackVjpCall&);
 template <template <typename> class MT> int policy_entry(const PolicyCall&);  // kernels_policy.hpp, policy_<model>.hip
 template <template <typename> class MT> int policy_episodes_entry(const EpisodeCall&);  // kernels_policy_episodes.hpp, policy_episodes_<model>.hip
+template <template <typename> class MT> int policy_vjp_entry(const PolicyVjpCall&);  // kernels_policy_vjp.hpp, policy_vjp_<model>.hip
 
 // The one choice of the element type: launcher<MT<float>, float>(call) or launcher<MT<double>, double>(call) by the call's dtype
 #define EXCENV_BY_DTYPE(launcher, MT, call) \
@@ -714,7 +716,7 @@ template <template <typename> class MT> struct EnvEntry {
   static EnvVTable vtable() {
     return EnvVTable{MT<float>::S, MT<float>::A, MT<float>::O, MT<float>::P, &step, &sim, &traj_gym, &from_obs, &update_ref,
                      &random_state, &observe, &vjp_entry<MT>, &rew_vjp_entry<MT>, &step_vjp_entry<MT>, &step_jac_entry<MT>,
-                     &feedback_entry<MT>, &feedback_vjp_entry<MT>, &policy_entry<MT>, &policy_episodes_entry<MT>};
+                     &feedback_entry<MT>, &feedback_vjp_entry<MT>, &policy_entry<MT>, &policy_episodes_entry<MT>, &policy_vjp_entry<MT>};
   }
 };
 

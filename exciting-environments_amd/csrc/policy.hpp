@@ -1,7 +1,9 @@
 // Policy rollouts: what one excenv_sim_policy call launches. Host-only and free of HIP, like feedback.hpp: the call record, what the
 // entry point refuses about the policy before any launch, the layout of the parameter array, the dynamic LDS of a launch and the
 // name of sim_policy_kernel (kernels_policy.hpp). Below them the same for excenv_sim_policy_episodes: the call with its episode
-// record, what the entry point refuses about that record, the name of sim_episodes_kernel (kernels_policy_episodes.hpp).
+// record, what the entry point refuses about that record, the name of sim_episodes_kernel (kernels_policy_episodes.hpp). Last the
+// reverse mode, excenv_sim_policy_vjp: its call, its LDS and bytes, its refusals and the name of sim_policy_vjp_kernel
+// (kernels_policy_vjp.hpp).
 #pragma once
 #include "closed_loop_call.hpp"
 
@@ -97,6 +99,61 @@ inline int episode_refusal(const excenv_episode_t* e, int S, int32_t substeps, c
   }
   if (e->end_mask == 0 && e->max_episode_steps == 0) {
     std::snprintf(msg, n, "%s: episode->end_mask = 0 and episode->max_episode_steps = 0: nothing can end an episode (use excenv_sim_policy)", fn);
+    return EXCENV_EINVAL;
+  }
+  return EXCENV_OK;
+}
+
+// ---- reverse mode of the policy rollout: excenv_sim_policy_vjp -----------------------------------------------------
+// The validated call: the stored forward of one excenv_sim_policy (or excenv_sim_policy_episodes) call, the cotangents of its outputs
+// and where the gradients go (include/excenv.h excenv_policy_vjp_t). Everything lane-major.
+struct PolicyVjpCall {
+  int solver, dtype;
+  int64_t B, K;
+  int32_t substeps;
+  const excenv_props_t* props;
+  const excenv_control_t* control;  // nullptr when n_control == 0; only n_control is read (references get no gradient)
+  double obs_stepsize, env_tau;
+  const excenv_policy_vjp_t* r;
+  void* stream;  // hipStream_t
+};
+
+// sim_policy_vjp_kernel<M, T, SOLVER> (kernels_policy_vjp.hpp): six models (no saturated PMSM), three solvers, both element types
+constexpr const char* policy_vjp_name() { return "sim_policy_vjp_kernel"; }
+
+// The dynamic LDS of its launch: every hidden layer of the lane's column at once, h[d_1 + .. + d_{L-1}][POLICY_BLOCK] (0 for L == 1);
+// at most 3 * 64 rows: 48 KB (fp32) / 96 KB (fp64)
+inline size_t policy_vjp_lds_bytes(const excenv_policy_t& p, size_t elem) {
+  size_t rows = 0;
+  for (int l = 1; l < p.n_layers; ++l) rows += (size_t)p.widths[l];
+  return rows * POLICY_BLOCK * elem;
+}
+
+// Algorithmic bytes per environment and action row of the reverse launch, w = elem: per solver step the saved row
+// (S) and the cotangent rows that are present (O of grad_obs: the control columns are skipped; S of grad_states); per action row the
+// stored observation row (OW), the applied action (A), grad_actions (A, present) in and grad_raw (A) out; one byte of the episode mask
+constexpr int64_t policy_vjp_bytes(int S, int A, int O, int elem, int n_control, int32_t substeps, bool has_grad_obs, bool has_grad_states,
+                                   bool has_grad_actions, bool has_reset) {
+  return (int64_t)elem * ((int64_t)substeps * (S + (has_grad_obs ? O : 0) + (has_grad_states ? S : 0)) + (O + n_control) +
+                          A * (2 + (has_grad_actions ? 1 : 0))) + (has_reset ? 1 : 0);
+}
+
+// What excenv_sim_policy_vjp refuses about its record for K action rows of `substeps` steps, behind excenv_sim_policy's checks of
+// the policy inside it: EXCENV_OK, or the code with the message in `msg`. NULL pointers first, then values.
+inline int policy_vjp_refusal(const excenv_policy_vjp_t* r, int64_t K, int32_t substeps, char* msg, size_t n) {
+  const char* fn = "excenv_sim_policy_vjp";
+  auto null = [&](const char* what) { std::snprintf(msg, n, "%s: %s is NULL", fn, what); return EXCENV_ENULL; };
+  if (!r->obs_traj) return null("call->obs_traj (the policy is evaluated again on the saved observation rows)");
+  if (!r->state_traj) return null("call->state_traj (the reverse pass reads the saved rows)");
+  if (K > 0 && !r->actions) return null("call->actions");
+  if (!r->grad_state0) return null("call->grad_state0");
+  if (K > 0 && !r->grad_raw) return null("call->grad_raw");
+  if (r->reset && substeps != 1) {
+    std::snprintf(msg, n, "%s: call->reset needs substeps == 1 (one solver step per action, as excenv_sim_policy_episodes; got %d)", fn, substeps);
+    return EXCENV_EINVAL;
+  }
+  if (K > (int64_t)0x7fffffff / substeps) {
+    std::snprintf(msg, n, "%s: K * substeps = %lld * %d rows exceed one launch", fn, (long long)K, (int)substeps);
     return EXCENV_EINVAL;
   }
   return EXCENV_OK;

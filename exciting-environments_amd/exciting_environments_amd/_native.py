@@ -111,6 +111,16 @@ class Policy(ctypes.Structure):
                 ("clip_hi", ctypes.c_double)]
 
 
+class PolicyVjp(ctypes.Structure):
+    """excenv_policy_vjp_t: the policy record and the stored forward of one excenv_sim_policy call, the cotangents of its outputs
+    and where the gradients go (excenv_sim_policy_vjp)."""
+
+    _fields_ = [("policy", Policy), ("obs_traj", ctypes.c_void_p), ("state_traj", ctypes.c_void_p), ("actions", ctypes.c_void_p),
+                ("reset", ctypes.c_void_p), ("grad_obs", ctypes.c_void_p), ("grad_states", ctypes.c_void_p),
+                ("grad_last_state", ctypes.c_void_p), ("grad_actions", ctypes.c_void_p), ("grad_state0", ctypes.c_void_p),
+                ("grad_raw", ctypes.c_void_p)]
+
+
 class Episode(ctypes.Structure):
     """excenv_episode_t: the reset rows, the end conditions and the gym / reset outputs of excenv_sim_policy_episodes."""
 
@@ -123,7 +133,8 @@ class Episode(ctypes.Structure):
 # the C types of the header's structures (tests/test_native_binding.py compares sizes and field offsets with the host compiler's)
 STRUCTS = {Param: "excenv_param_t", PmsmLut: "excenv_pmsm_lut_t", Props: "excenv_props_t", LaunchOpts: "excenv_launch_opts_t",
            TrajGym: "excenv_traj_gym_t", Control: "excenv_control_t", Feedback: "excenv_feedback_t",
-           FeedbackVjp: "excenv_feedback_vjp_t", Policy: "excenv_policy_t", Episode: "excenv_episode_t"}
+           FeedbackVjp: "excenv_feedback_vjp_t", Policy: "excenv_policy_t", Episode: "excenv_episode_t",
+           PolicyVjp: "excenv_policy_vjp_t"}
 
 _vp, _ci, _i32, _i64, _cd = ctypes.c_void_p, ctypes.c_int, ctypes.c_int32, ctypes.c_int64, ctypes.c_double
 _STEP = [_ci, _ci, _ci, _i64, _vp, _vp, _cd, _vp, _vp, _vp, _vp]  # env, solver, dtype, B, props, control, tau, in, action, out, obs
@@ -183,6 +194,10 @@ PROTOTYPES = {
     "excenv_sim_feedback_vjp_bytes": (_i64, [_ci, _ci, _i32, _i32, _ci, _ci, _ci, _ci]),
     # env, solver, dtype, B, K, substeps, props, control, obs_stepsize, env_tau, call, workspace, workspace_bytes, opts, stream
     "excenv_sim_feedback_vjp": (_ci, [_ci, _ci, _ci, _i64, _i64, _i32, _vp, _vp, _cd, _cd, _vp, _vp, _i64, _vp, _vp]),
+    # env, dtype, n_control, substeps, has_grad_obs, has_grad_states, has_grad_actions, has_reset
+    "excenv_sim_policy_vjp_bytes": (_i64, [_ci, _ci, _i32, _i32, _ci, _ci, _ci, _ci]),
+    # env, solver, dtype, B, K, substeps, props, control, obs_stepsize, env_tau, call, opts, stream
+    "excenv_sim_policy_vjp": (_ci, [_ci, _ci, _ci, _i64, _i64, _i32, _vp, _vp, _cd, _cd, _vp, _vp, _vp]),
     "excenv_state_from_observation": (_ci, [_ci, _ci, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "excenv_update_ref": (_ci, [_ci, _ci, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
     "excenv_observe": (_ci, [_ci, _ci, _i64, _vp, _vp, _vp, _vp, _vp]),

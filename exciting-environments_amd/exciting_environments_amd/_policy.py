@@ -3,8 +3,9 @@
 observation row it has just saved, plus an optional pre-sampled exploration row, clamped. Mixed into
 `CoreEnvironment` (core_env.py); `MLPPolicy` is the parameter record; what the call shares with `vmap_sim_ahead_feedback`
 is _closed_loop.py's. `vmap_rollout_episodes` is the same rollout with rewards, flags, a step budget and resets inside the launch
-(sim_episodes_kernel through `excenv_sim_policy_episodes`). Nothing here records a graph: a training loop recomputes log-probabilities from the returned observation
-rows and actions with torch's own autograd."""
+(sim_episodes_kernel through `excenv_sim_policy_episodes`). Nothing here records a graph: a likelihood-ratio
+training loop recomputes log-probabilities from the returned observation rows and actions with torch's own autograd, and
+`vmap_sim_ahead_policy(..., differentiable=True)` hands over to the reverse mode of _policy_vjp.py."""
 from __future__ import annotations
 
 import collections
@@ -72,10 +73,28 @@ class MLPPolicy:
             off += d * (n + 1)
         return out
 
+    def torch_forward(self, rows, params=None):
+        """The network as differentiable torch operations: rows [..., d_0] -> [..., d_L], the pre-clamp output without noise.
+        `params`: a flat tensor laid out like `self.params` (the default), whose views serve as the weights, so
+        `torch.autograd.grad(policy.torch_forward(rows, p), p, g)` is the parameter gradient of the rows."""
+        p = self.params if params is None else params
+        act = torch.tanh if self.activation == "tanh" else torch.relu
+        x, off, L = rows, 0, self.n_layers
+        for l, (n, d) in enumerate(zip(self.widths[:-1], self.widths[1:])):
+            x = torch.nn.functional.linear(x, p[off:off + d * n].view(d, n), p[off + d * n:off + d * (n + 1)])
+            if l < L - 1:
+                x = act(x)
+            off += d * (n + 1)
+        return x
+
     @classmethod
-    def from_torch(cls, module, device=None, dtype=None):
+    def from_torch(cls, module, device=None, dtype=None, track=False):
         """From an `nn.Sequential` of `nn.Linear` layers (with bias) separated by one kind of `nn.Tanh` / `nn.ReLU`; anything else
-        is a ValueError that names it. The parameters are copied (detached)."""
+        is a ValueError that names it. The parameters are copied (detached).
+
+        track=True: `params` is instead a `torch.cat` of the module's live parameters with its graph kept, so a backward through
+        `vmap_sim_ahead_policy(..., differentiable=True)` fills the module's `.grad`. It is a SNAPSHOT of the values: an optimiser
+        step changes the module, not this tensor — build the policy again after every step."""
         nn = torch.nn
         if not isinstance(module, nn.Sequential):
             raise ValueError(f"MLPPolicy.from_torch: needs an nn.Sequential of Linear layers, got {type(module).__name__}")
@@ -104,7 +123,11 @@ class MLPPolicy:
                 raise ValueError(f"MLPPolicy.from_torch: hidden layer {j + 1} has {m.out_features} units; 1 to "
                                  f"{_native.POLICY_MAX_WIDTH} are supported")
         activation = "relu" if nn.ReLU in kinds else "tanh"
-        return cls([m.weight for m in linears], [m.bias for m in linears], activation, device=device, dtype=dtype)
+        policy = cls([m.weight for m in linears], [m.bias for m in linears], activation, device=device, dtype=dtype)
+        if track:
+            live = torch.cat([t.reshape(-1) for m in linears for t in (m.weight, m.bias)])
+            policy.params = live.to(device=policy.params.device, dtype=policy.params.dtype)
+        return policy
 
 
 # what `vmap_rollout_episodes` returns: zero-copy views of lane-major memory (`states` is None without a state trajectory)
@@ -116,12 +139,17 @@ class PolicyMixin:
     # excenv_last_launch() of the most recent excenv_sim_policy / excenv_sim_policy_episodes launch of this environment
     last_policy_launch = ""
 
-    def _policy_call(self, fn, init_state, policy, noise, n_actions, obs_stepsize, action_stepsize, clip):
-        """The checks and the excenv_policy_t record both policy launches share -> (record, its tensors to keep alive, K, substeps)"""
+    def _policy_wants_grad(self, init_state, policy, noise):
+        """Does the policy's parameter tensor, the noise or a leaf of the initial physical state require grad?"""
+        tensors = [getattr(policy, "params", None), noise] + [getattr(init_state.physical_state, n) for n in self.STATE_FIELDS]
+        return any(isinstance(t, torch.Tensor) and t.requires_grad for t in tensors)
+
+    def _policy_call(self, fn, init_state, policy, noise, n_actions, obs_stepsize, action_stepsize, clip, recording=False):
+        """The checks and the excenv_policy_t record both policy launches share -> (record, its tensors to keep alive, K, substeps).
+        recording: the forward of the autograd node of _policy_vjp.py, which owns the gradients of these inputs."""
         assert isinstance(policy, MLPPolicy), f"policy needs to be an MLPPolicy, but {type(policy).__name__} is given"
-        tensors = [policy.params, noise] + [getattr(init_state.physical_state, n) for n in self.STATE_FIELDS]
-        wants = any(isinstance(t, torch.Tensor) and t.requires_grad for t in tensors)
-        if self.differentiable and torch.is_grad_enabled() and (self._param_leaves() or wants):
+        wants = not recording and self._policy_wants_grad(init_state, policy, noise)
+        if not recording and self.differentiable and torch.is_grad_enabled() and (self._param_leaves() or wants):
             raise ValueError(f"{fn}: env.differentiable with an input that requires grad: there is no reverse mode through the policy "
                              "launch; detach the inputs or set env.differentiable = False, and recompute the log-probabilities from "
                              "the returned observations and actions in torch")
@@ -139,7 +167,8 @@ class PolicyMixin:
                                 _native._ptr(noise) if K > 0 else None, lo, hi)
         return record, (params, noise), K, sub
 
-    def vmap_sim_ahead_policy(self, init_state, policy, n_actions, obs_stepsize, action_stepsize, noise=None, clip=(-1.0, 1.0)):
+    def vmap_sim_ahead_policy(self, init_state, policy, n_actions, obs_stepsize, action_stepsize, noise=None, clip=(-1.0, 1.0),
+                              differentiable=None):
         """Rollouts of all batch_size environments under an MLP policy in one kernel launch -> (observations [B, N+1, OW], states
         with leaves [B, N+1], last_state with leaves [B], actions [B, K, A]), K = n_actions action rows of substeps = action_stepsize
         / obs_stepsize solver steps each, N = K * substeps.
@@ -156,10 +185,26 @@ class PolicyMixin:
         The returned tensors are views of freshly allocated lane-major memory and carry no graph; `states` is None with
         `env.store_state_trajectory = False`. `vmap_generate_rew_trunc_term_ahead(states, actions)` gives the gym outputs.
         Refused by name (ValueError): trajectory layouts other than "lane_major", `sim_ahead_semantics == "ahead_accumulated_t"`,
-        and `env.differentiable` with an input or parameter that requires grad (there is no reverse mode through this launch)."""
+        and (differentiable=None, the default) `env.differentiable` with an input or parameter that requires grad (there is no
+        reverse mode through this launch).
+
+        differentiable=True: when grad mode is on and `policy.params`, the noise or a leaf of the initial physical state requires
+        grad, the call records ONE autograd node (_policy_vjp.py) whose backward is one `vmap_sim_ahead_policy_vjp` call;
+        observations, state leaves, last state and actions carry the graph, so a loss through
+        `vmap_generate_rew_trunc_term_ahead(states, actions)` under `env.differentiable` reaches `policy.params.grad` (and, with
+        `MLPPolicy.from_torch(module, track=True)`, the module's `.grad`). With no input that requires grad the plain path runs.
+        Refused then: `store_state_trajectory = False`, static parameters that require grad, the saturated PMSM, per-environment
+        properties, graph capture. No second derivatives."""
         fn = "vmap_sim_ahead_policy"
         _closed_loop.refuse_settings(self, fn, "policy")
-        record, _keep, K, sub = self._policy_call(fn, init_state, policy, noise, n_actions, obs_stepsize, action_stepsize, clip)
+        if differentiable and torch.is_grad_enabled() and (self._param_leaves() or self._policy_wants_grad(init_state, policy, noise)):
+            return self._policy_differentiable(init_state, policy, n_actions, obs_stepsize, action_stepsize, noise, clip)
+        return self._policy_launch(fn, init_state, policy, n_actions, obs_stepsize, action_stepsize, noise, clip)
+
+    def _policy_launch(self, fn, init_state, policy, n_actions, obs_stepsize, action_stepsize, noise, clip, recording=False):
+        """The one excenv_sim_policy launch behind vmap_sim_ahead_policy (its return value); records no graph."""
+        record, _keep, K, sub = self._policy_call(fn, init_state, policy, noise, n_actions, obs_stepsize, action_stepsize, clip,
+                                                  recording=recording)
         out, name = _closed_loop.launch(self, "excenv_sim_policy", record, fn, init_state, K, sub, obs_stepsize)
         if name is not None:
             self.last_policy_launch = name
@@ -205,7 +250,8 @@ class PolicyMixin:
         row (the reference's semantics): "terminated" in `end_on` then resets on every step, `end_on=("truncated",)` is the usual
         choice there. episode_steps of the result carries over to the next call.
 
-        Refused by name (ValueError): what `vmap_sim_ahead_policy` refuses, an unknown `end_on` entry, and `end_on=()` with
+        No recording form: `vmap_sim_ahead_policy_vjp(policy, observations, states, actions, ..., reset=result.reset)` is the route
+        to gradients. Refused by name (ValueError): what `vmap_sim_ahead_policy` refuses, an unknown `end_on` entry, and `end_on=()` with
         `max_episode_steps=0` (nothing can end an episode: that is `vmap_sim_ahead_policy`)."""
         fn = "vmap_rollout_episodes"
         _closed_loop.refuse_settings(self, fn, "episode")

@@ -32,6 +32,7 @@ from ._reward_vjp import RewardVjpMixin
 from ._feedback import FeedbackMixin
 from ._feedback_vjp import FeedbackVjpMixin
 from ._policy import PolicyMixin
+from ._policy_vjp import PolicyVjpMixin
 from ._linearize import LinearizeMixin
 from ._step_vjp import StepVjpMixin
 from ._vjp import TrajectoryVjpMixin
@@ -50,7 +51,7 @@ def _is_scalar(x) -> bool:
 
 
 class CoreEnvironment(TrajectoryLaunchMixin, TrajectoryVjpMixin, RewardVjpMixin, StepVjpMixin, LinearizeMixin, FeedbackMixin,
-                      FeedbackVjpMixin, PolicyMixin, ABC):
+                      FeedbackVjpMixin, PolicyMixin, PolicyVjpMixin, ABC):
     """Core structure of the provided environments (reference core_env.py:15-57).
 
     The simulated systems are physical state-space models dx/dt = f(x(t), u(t)); outputs are

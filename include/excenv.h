@@ -644,6 +644,68 @@ int excenv_sim_feedback_vjp(int env, int solver, int dtype, int64_t B, int64_t K
                             const excenv_feedback_vjp_t* call, void* workspace, int64_t workspace_bytes,
                             const excenv_launch_opts_t* opts, void* stream);
 
+/* ---- reverse mode of excenv_sim_policy: the vector-Jacobian product of one policy rollout with respect to the initial state and the
+ * pre-clamp output of the network at every action row, from the rows that call saved (additions, same ABI version: a binder probes
+ * for the symbols). The forward is excenv_sim_policy's contract. ONE launch of sim_policy_vjp_kernel, one environment per lane; it
+ * has no cross-lane reduction and computes NO parameter gradient: with obs_k the saved observation row of action row k,
+ *   grad_params = sum over b, k of (d mlp / d params)(obs[b][k])^T grad_raw[b][k],
+ * a contraction over B * K independent samples that the caller does with its own BLAS on the rows the forward saved.
+ * The reverse pass walks the rows from N down to 0 and carries sb[S] (cotangent of the carried state) and ab[A] (the action cotangent
+ * summed over the `substeps` steps that held a_k), exactly as excenv_sim_feedback_vjp does. Per solver step n = N-1 .. 0:
+ *   1. sb += observe^T(grad_obs[n+1]) + grad_states[n+1] at the saved row n+1 (row N also takes grad_last_state). The control columns
+ *      of grad_obs are skipped: references get no gradient.
+ *   2. the transposed step of excenv_step_vjp takes sb from row n+1 back to row n, and ab += its action gradient.
+ *   3. if n is an action row (n = k * substeps):
+ *        ab += grad_actions[k]
+ *        pre[q] = ab[q] where clip_lo < a_k[q] < clip_hi (the stored applied action), else 0;   ab = 0
+ *        grad_raw[k] = pre                     (= the cotangent of noise[k] and of the network output x^L)
+ *        x^0 .. x^{L-1}: the forward's statements again on the STORED observation row n (all OW columns), every layer kept
+ *        d^L = pre
+ *        for l = L .. 1:  xb[i] = 0;  xb[i] = fma(W_l[j][i], d^l[j], xb[i]) for j = 0 .. d_l - 1, in this order
+ *                         (for l = 1 only i < O: reference columns get no gradient)
+ *                         d^{l-1}[i] = xb[i] * act'(x^{l-1}[i])   for l > 1
+ *        sb += observe^T(xb of layer 1) at s_n
+ *   4. after row 0: sb += observe^T(grad_obs[0]) + grad_states[0]; grad_state0 = sb.
+ * act' is taken from the recomputed activation value h = x^{l-1}[i]: EXCENV_ACT_RELU passes xb where h > 0 and gives 0 elsewhere
+ * (torch's convention; a NaN gets 0), EXCENV_ACT_TANH multiplies by 1 - h * h (a rounded product, then a rounded difference). The
+ * clamp has derivative 0 on and outside its bounds; a NaN compares false, so its gradient is 0. The other subgradient conventions
+ * are excenv_sim_ahead_vjp's.
+ * Episode mask (optional, substeps == 1): reset is what excenv_sim_policy_episodes wrote. Where reset[n] != 0, step n -> n+1 was a
+ * reset: the transposed step is skipped and what was accumulated for row n+1 is dropped (sb = 0: reset states get no gradient), and
+ * ab holds grad_actions[n] only (the action was written but not applied). Step 3 then runs as usual.
+ *   control             : only n_control is read (the reference columns come from the stored observation rows)
+ *   policy              : the excenv_policy_t of the forward; `noise` is not read
+ *   obs_traj, state_traj, actions : what the forward wrote ([N+1][OW][B], S x [N+1][B], [K][A][B]); all three are required
+ *                         (actions with K > 0)
+ *   reset               : [K][B] bytes or NULL
+ *   grad_obs            : [N+1][OW][B] or NULL;  grad_states, grad_last_state: NULL, or S pointers ([N+1][B] / [B], or NULL each)
+ *   grad_actions        : [K][A][B] or NULL (cotangent of actions_out)
+ *   grad_state0         : (out) S pointers to [B];  grad_raw: (out) [K][A][B]; both required (grad_raw with K > 0)
+ * Needs no workspace; never allocates or synchronises. K == 0 handles row 0 only; B == 0 returns EXCENV_OK without a launch.
+ * excenv_last_launch() reports "sim_policy_vjp_kernel". Validated before any HIP call in excenv_sim_policy's order under this entry's
+ * name (a NULL `call` first of all), then this record: EXCENV_ENULL names a missing required pointer; EXCENV_EINVAL: reset with
+ * substeps != 1, K * substeps >= 2^31. EXCENV_EUNSUPPORTED: the saturated PMSM (pmsm_lut), per-environment property arrays.
+ * excenv_sim_policy_vjp_bytes (host only): the algorithmic bytes per environment and action row: w * (substeps * (S + O [grad_obs] +
+ * S [grad_states]) + OW + A * (2 + [grad_actions])) + [reset]; -1 for a bad argument. */
+typedef struct {
+  excenv_policy_t policy;              /* the forward's record; noise is not read */
+  const void* obs_traj;                /* [N+1][OW][B], required */
+  const void* const* state_traj;       /* S x [N+1][B], required */
+  const void* actions;                 /* [K][A][B]: the applied actions */
+  const uint8_t* reset;                /* [K][B] or NULL; needs substeps == 1 */
+  const void* grad_obs;                /* [N+1][OW][B] or NULL */
+  const void* const* grad_states;      /* NULL, or S pointers ([N+1][B] or NULL each) */
+  const void* const* grad_last_state;  /* NULL, or S pointers ([B] or NULL each) */
+  const void* grad_actions;            /* [K][A][B] or NULL */
+  void* const* grad_state0;            /* (out) S x [B] */
+  void* grad_raw;                      /* (out) [K][A][B] */
+} excenv_policy_vjp_t;
+int64_t excenv_sim_policy_vjp_bytes(int env, int dtype, int32_t n_control, int32_t substeps, int has_grad_obs, int has_grad_states,
+                                    int has_grad_actions, int has_reset);
+int excenv_sim_policy_vjp(int env, int solver, int dtype, int64_t B, int64_t K, int32_t substeps, const excenv_props_t* props,
+                          const excenv_control_t* control, double obs_stepsize, double env_tau, const excenv_policy_vjp_t* call,
+                          const excenv_launch_opts_t* opts, void* stream);
+
 /* ---- replaces CoreEnvironment.vmap_generate_state_from_observation (core_env.py:689-705; per env e.g.
  * pendulum_env.py:331-364, pmsm_env.py:921-970): obs [B][O + n_control] row-major -> denormalised physical state leaves
  * state_out[S][B] and, for each controlled field control_idx[j], its denormalised reference leaf reference_out[j][B]
