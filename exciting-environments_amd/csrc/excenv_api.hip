@@ -23,6 +23,7 @@ void set_error(const char* fmt, ...) {
 
 int launch_transpose(int dtype, int64_t M, int64_t N, const void* in, void* out, hipStream_t stream);
 int launch_param_sum(int dtype, int64_t B, int n, const void* const* per_env, void* out, void* workspace, hipStream_t stream);
+int launch_policy_param_grad(int dtype, int64_t B, int64_t K, int32_t substeps, const excenv_policy_param_grad_t& call, hipStream_t stream);
 
 EnvVTable vtable_pendulum();
 EnvVTable vtable_msd();
@@ -833,6 +834,23 @@ int excenv_sim_policy_vjp(int env, int solver, int dtype, int64_t B, int64_t K, 
   if (int rc = check_broadcast_props(fn, env, props)) return rc;
   const PolicyVjpCall vc{solver, dtype, B, K, substeps, props, control, obs_stepsize, env_tau, call, stream};
   return t->sim_policy_vjp(vc);
+}
+
+int64_t excenv_policy_param_grad_workspace_bytes(int dtype, int64_t B, int64_t K, const excenv_policy_t* policy, int32_t max_groups) {
+  if ((dtype != EXCENV_F32 && dtype != EXCENV_F64) || B < 0 || K < 0 || !policy || max_groups < 0) return -1;
+  if (policy->n_layers < 1 || policy->n_layers > EXCENV_POLICY_MAX_LAYERS) return -1;
+  for (int l = 0; l <= policy->n_layers; ++l)
+    if (policy->widths[l] < 1 || policy->widths[l] > EXCENV_POLICY_MAX_WIDTH) return -1;
+  return policy_param_grad_workspace(B, K, *policy, max_groups);
+}
+
+int excenv_policy_param_grad(int dtype, int64_t B, int64_t K, int32_t substeps, const excenv_policy_param_grad_t* call, void* stream) {
+  {
+    char why[256];
+    if (int rc = policy_param_grad_refusal(dtype, B, K, substeps, call, why, sizeof(why))) { set_error("%s", why); return rc; }
+  }
+  if (B == 0) return EXCENV_OK;
+  return launch_policy_param_grad(dtype, B, K, substeps, *call, (hipStream_t)stream);
 }
 
 int excenv_state_from_observation(int env, int dtype, int64_t B, const excenv_props_t* props, int32_t n_control,

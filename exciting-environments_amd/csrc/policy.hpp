@@ -3,7 +3,8 @@
 // name of sim_policy_kernel (kernels_policy.hpp). Below them the same for excenv_sim_policy_episodes: the call with its episode
 // record, what the entry point refuses about that record, the name of sim_episodes_kernel (kernels_policy_episodes.hpp). Last the
 // reverse mode, excenv_sim_policy_vjp: its call, its LDS and bytes, its refusals and the name of sim_policy_vjp_kernel
-// (kernels_policy_vjp.hpp).
+// (kernels_policy_vjp.hpp), and the parameter gradient, excenv_policy_param_grad: its tiles, workgroups, LDS, workspace and refusals
+// (policy_param_grad.hip).
 #pragma once
 #include "closed_loop_call.hpp"
 
@@ -154,6 +155,109 @@ inline int policy_vjp_refusal(const excenv_policy_vjp_t* r, int64_t K, int32_t s
   }
   if (K > (int64_t)0x7fffffff / substeps) {
     std::snprintf(msg, n, "%s: K * substeps = %lld * %d rows exceed one launch", fn, (long long)K, (int)substeps);
+    return EXCENV_EINVAL;
+  }
+  return EXCENV_OK;
+}
+
+// ---- the parameter gradient of a policy rollout: excenv_policy_param_grad ------------------------------------------
+// policy_param_grad_kernel<T> and policy_param_grad_reduce_kernel<T> (policy_param_grad.hip): no model, one instantiation per type
+constexpr const char* policy_param_grad_name() { return "policy_param_grad_kernel"; }
+
+constexpr int PARAM_GRAD_BLOCK = 256;  // four waves
+constexpr int PARAM_GRAD_TILE = 64;    // samples of one tile: 64 consecutive environments of one action row
+// The row stride of the tile in LDS, in elements: 2 mod 32, so that the sixteen rows j0 + (l & 15) at the two columns s0 + (l >> 4) of
+// a 32-lane group (the operand reads of the weight product) fall on 32 different banks, in 4-byte and in 8-byte elements
+constexpr int PARAM_GRAD_LDS_STRIDE = PARAM_GRAD_TILE + 2;
+// 16 x 16 output tiles of the weight product a wave holds in registers: the widest network has 8 + 20 + 20 + 5 = 53 over four waves
+constexpr int PARAM_GRAD_SLOTS = 14;
+
+// The rows of the tile in LDS: x^0 (OW), every hidden x^l (d^l over it in place), d^L (A) and the ones row of the bias sums
+inline int policy_param_grad_lds_rows(const excenv_policy_t& p) {
+  int rows = p.widths[0] + p.widths[p.n_layers] + 1;
+  for (int l = 1; l < p.n_layers; ++l) rows += p.widths[l];
+  return rows;
+}
+inline size_t policy_param_grad_lds_bytes(const excenv_policy_t& p, size_t elem) {
+  return (size_t)policy_param_grad_lds_rows(p) * PARAM_GRAD_LDS_STRIDE * elem;
+}
+// 16 x 16 output tiles of all the weight products: per layer ceil(d_l / 16) x ceil((d_{l-1} + 1) / 16), the bias as one more column
+inline int policy_param_grad_out_tiles(const excenv_policy_t& p) {
+  int n = 0;
+  for (int l = 1; l <= p.n_layers; ++l) n += ((p.widths[l] + 15) / 16) * ((p.widths[l - 1] + 1 + 15) / 16);
+  return n;
+}
+
+// Sample tiles of a call, its workgroups and the first tile of workgroup g (g == groups: one past the last tile): functions of
+// (B, K, max_groups) only
+inline int64_t policy_param_grad_tiles(int64_t B, int64_t K) { return K * ((B + PARAM_GRAD_TILE - 1) / PARAM_GRAD_TILE); }
+inline int64_t policy_param_grad_groups(int64_t B, int64_t K, int32_t max_groups) {
+  const int64_t tiles = policy_param_grad_tiles(B, K), cap = max_groups > 0 ? max_groups : EXCENV_PARAM_GRAD_AUTO_GROUPS;
+  return tiles < cap ? tiles : cap;
+}
+// (every workgroup gets floor(tiles / groups) tiles, the first tiles % groups of them one more)
+inline int64_t policy_param_grad_first_tile(int64_t tiles, int64_t groups, int64_t g) {
+  const int64_t q = tiles / groups, r = tiles % groups;
+  return g * q + (g < r ? g : r);
+}
+inline int64_t policy_param_grad_workspace(int64_t B, int64_t K, const excenv_policy_t& p, int32_t max_groups) {
+  return policy_param_grad_groups(B, K, max_groups) * policy_param_count(p) * 8;
+}
+
+// What excenv_policy_param_grad refuses: EXCENV_OK, or the code with the message in `msg`. NULL pointers first, then values.
+inline int policy_param_grad_refusal(int dtype, int64_t B, int64_t K, int32_t substeps, const excenv_policy_param_grad_t* c, char* msg,
+                                     size_t n) {
+  const char* fn = "excenv_policy_param_grad";
+  auto null = [&](const char* what) { std::snprintf(msg, n, "%s: %s is NULL", fn, what); return EXCENV_ENULL; };
+  if (!c) return null("call");
+  const excenv_policy_t& p = c->policy;
+  if (!p.params) return null("call->policy.params");
+  if (!c->obs_traj) return null("call->obs_traj");
+  if (K > 0 && !c->grad_raw) return null("call->grad_raw");
+  if (!c->grad_params) return null("call->grad_params");
+  if (!c->workspace) return null("call->workspace");
+  if (dtype != EXCENV_F32 && dtype != EXCENV_F64) {
+    std::snprintf(msg, n, "%s: dtype must be EXCENV_F32 (0) or EXCENV_F64 (1) (got %d)", fn, dtype);
+    return EXCENV_EINVAL;
+  }
+  if (B < 0 || K < 0 || substeps < 1) {
+    std::snprintf(msg, n, "%s: bad B=%lld, K=%lld or substeps=%d", fn, (long long)B, (long long)K, (int)substeps);
+    return EXCENV_EINVAL;
+  }
+  if (K > (int64_t)0x7fffffff / substeps) {
+    std::snprintf(msg, n, "%s: K * substeps = %lld * %d rows exceed one launch", fn, (long long)K, (int)substeps);
+    return EXCENV_EINVAL;
+  }
+  if (p.n_layers < 1 || p.n_layers > EXCENV_POLICY_MAX_LAYERS) {
+    std::snprintf(msg, n, "%s: policy.n_layers must be 1 .. %d (got %d)", fn, EXCENV_POLICY_MAX_LAYERS, p.n_layers);
+    return EXCENV_EINVAL;
+  }
+  for (int l = 1; l < p.n_layers; ++l) {
+    if (p.widths[l] < 1 || p.widths[l] > EXCENV_POLICY_MAX_WIDTH) {
+      std::snprintf(msg, n, "%s: policy.widths[%d] must be 1 .. %d (got %d)", fn, l, EXCENV_POLICY_MAX_WIDTH, p.widths[l]);
+      return EXCENV_EINVAL;
+    }
+  }
+  if (p.widths[0] < 1 || p.widths[0] > EXCENV_POLICY_MAX_INPUT) {
+    std::snprintf(msg, n, "%s: policy.widths[0] must be 1 .. %d (the widest observation row; got %d)", fn, EXCENV_POLICY_MAX_INPUT, p.widths[0]);
+    return EXCENV_EINVAL;
+  }
+  if (p.widths[p.n_layers] < 1 || p.widths[p.n_layers] > EXCENV_MAX_ACTION) {
+    std::snprintf(msg, n, "%s: policy.widths[%d] must be 1 .. %d (the action width; got %d)", fn, p.n_layers, EXCENV_MAX_ACTION,
+                  p.widths[p.n_layers]);
+    return EXCENV_EINVAL;
+  }
+  if (p.activation != EXCENV_ACT_RELU && p.activation != EXCENV_ACT_TANH) {
+    std::snprintf(msg, n, "%s: policy.activation must be EXCENV_ACT_RELU (0) or EXCENV_ACT_TANH (1) (got %d)", fn, p.activation);
+    return EXCENV_EINVAL;
+  }
+  if (c->max_groups < 0) {
+    std::snprintf(msg, n, "%s: call->max_groups must not be negative (got %d; 0: auto)", fn, c->max_groups);
+    return EXCENV_EINVAL;
+  }
+  const int64_t need = policy_param_grad_workspace(B, K, p, c->max_groups);
+  if (c->workspace_bytes < need || (reinterpret_cast<uintptr_t>(c->workspace) & 7u) != 0) {
+    std::snprintf(msg, n, "%s: needs an 8-byte aligned workspace of %lld bytes (excenv_policy_param_grad_workspace_bytes)", fn, (long long)need);
     return EXCENV_EINVAL;
   }
   return EXCENV_OK;

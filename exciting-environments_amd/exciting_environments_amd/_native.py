@@ -31,6 +31,9 @@ OPT_NO_FUSED_ACTIONS = 1  # EXCENV_OPT_NO_FUSED_ACTIONS
 OPT_KEEP_CONSTANT_COLUMNS = 2  # EXCENV_OPT_KEEP_CONSTANT_COLUMNS
 ABI_VERSION = 7
 POLICY_MAX_LAYERS, POLICY_MAX_WIDTH = 4, 64  # excenv_policy_t: linear layers of the MLP, units of a hidden layer
+POLICY_MAX_INPUT = 16  # excenv_policy_param_grad: the widest observation row, 8 + MAX_CONTROL
+PARAM_GRAD_CHAIN = 4096  # samples one working-dtype accumulator of policy_param_grad_kernel sums before it goes to fp64
+PARAM_GRAD_AUTO_GROUPS = 512  # its workgroups with max_groups == 0, at most
 ACT_RELU, ACT_TANH = 0, 1
 ACTIVATIONS = {"relu": ACT_RELU, "tanh": ACT_TANH}
 END_TERMINATED, END_TRUNCATED = 1, 2  # excenv_episode_t.end_mask
@@ -121,6 +124,14 @@ class PolicyVjp(ctypes.Structure):
                 ("grad_raw", ctypes.c_void_p)]
 
 
+class PolicyParamGrad(ctypes.Structure):
+    """excenv_policy_param_grad_t: the network, the saved observation rows, the cotangent rows excenv_sim_policy_vjp wrote, where the
+    parameter gradient goes and the workspace of the two launches (excenv_policy_param_grad)."""
+
+    _fields_ = [("policy", Policy), ("obs_traj", ctypes.c_void_p), ("grad_raw", ctypes.c_void_p), ("grad_params", ctypes.c_void_p),
+                ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_int64), ("max_groups", ctypes.c_int32)]
+
+
 class Episode(ctypes.Structure):
     """excenv_episode_t: the reset rows, the end conditions and the gym / reset outputs of excenv_sim_policy_episodes."""
 
@@ -134,7 +145,7 @@ class Episode(ctypes.Structure):
 STRUCTS = {Param: "excenv_param_t", PmsmLut: "excenv_pmsm_lut_t", Props: "excenv_props_t", LaunchOpts: "excenv_launch_opts_t",
            TrajGym: "excenv_traj_gym_t", Control: "excenv_control_t", Feedback: "excenv_feedback_t",
            FeedbackVjp: "excenv_feedback_vjp_t", Policy: "excenv_policy_t", Episode: "excenv_episode_t",
-           PolicyVjp: "excenv_policy_vjp_t"}
+           PolicyVjp: "excenv_policy_vjp_t", PolicyParamGrad: "excenv_policy_param_grad_t"}
 
 _vp, _ci, _i32, _i64, _cd = ctypes.c_void_p, ctypes.c_int, ctypes.c_int32, ctypes.c_int64, ctypes.c_double
 _STEP = [_ci, _ci, _ci, _i64, _vp, _vp, _cd, _vp, _vp, _vp, _vp]  # env, solver, dtype, B, props, control, tau, in, action, out, obs
@@ -198,6 +209,10 @@ PROTOTYPES = {
     "excenv_sim_policy_vjp_bytes": (_i64, [_ci, _ci, _i32, _i32, _ci, _ci, _ci, _ci]),
     # env, solver, dtype, B, K, substeps, props, control, obs_stepsize, env_tau, call, opts, stream
     "excenv_sim_policy_vjp": (_ci, [_ci, _ci, _ci, _i64, _i64, _i32, _vp, _vp, _cd, _cd, _vp, _vp, _vp]),
+    # dtype, B, K, policy, max_groups
+    "excenv_policy_param_grad_workspace_bytes": (_i64, [_ci, _i64, _i64, _vp, _i32]),
+    # dtype, B, K, substeps, call, stream
+    "excenv_policy_param_grad": (_ci, [_ci, _i64, _i64, _i32, _vp, _vp]),
     "excenv_state_from_observation": (_ci, [_ci, _ci, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "excenv_update_ref": (_ci, [_ci, _ci, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
     "excenv_observe": (_ci, [_ci, _ci, _i64, _vp, _vp, _vp, _vp, _vp]),

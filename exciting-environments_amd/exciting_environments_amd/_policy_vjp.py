@@ -24,6 +24,19 @@ from ._reverse import _leaf_list, cotangent, count_control, opt_ptrs
 
 # samples (environments x action rows) per pass of the parameter contraction: bounds the hidden activations torch materialises
 PARAM_CHUNK = 2 ** 21
+# `param_grads=` of vmap_sim_ahead_policy_vjp: the torch contraction (True: what it always meant), none, or excenv_policy_param_grad
+PARAM_GRAD_ROUTES = (True, "torch", False, "fused")
+
+
+def _param_grad_route(param_grads):
+    """-> "torch", "fused" or None (no parameter gradient)"""
+    if param_grads is True or (isinstance(param_grads, str) and param_grads == "torch"):
+        return "torch"
+    if param_grads is False:
+        return None
+    if isinstance(param_grads, str) and param_grads == "fused":
+        return "fused"
+    raise ValueError(f"vmap_sim_ahead_policy_vjp: param_grads needs to be one of True, 'torch', False or 'fused', but {param_grads!r} is given")
 
 
 class _PolicyRollout(torch.autograd.Function):
@@ -56,7 +69,7 @@ class _PolicyRollout(torch.autograd.Function):
         gs, g_noise, g_params = env._policy_vjp_launch(
             ctx.policy, obs, traj, actions, ctx.steps[0], ctx.steps[1], ctx.clip, g_obs,
             g_states if any(t is not None for t in g_states) else None, g_last if any(t is not None for t in g_last) else None,
-            g_act, None, need[6], packed=ctx.packed)
+            g_act, None, env.policy_param_grads if need[6] else False, packed=ctx.packed)
 
         def like(t, j, wanted):  # the gradient in the shape, device and dtype the input had
             if t is None or ctx.meta[j] is None or not wanted:
@@ -72,6 +85,72 @@ class PolicyVjpMixin:
     # excenv_last_launch() of the most recent excenv_sim_policy_vjp call of this environment, read on the thread that enqueued it
     # (autograd runs backward on a thread of its own)
     last_policy_vjp_launch = ""
+    _policy_param_grads = "torch"
+
+    @property
+    def policy_param_grads(self):
+        """What `param_grads=True` means in the recording form (`vmap_sim_ahead_policy(differentiable=True)`): "torch", the
+        contraction in torch (the default), or "fused", one excenv_policy_param_grad call on the matrix cores."""
+        return self._policy_param_grads
+
+    @policy_param_grads.setter
+    def policy_param_grads(self, value):
+        if not (isinstance(value, str) and value in ("torch", "fused")):
+            raise ValueError(f"policy_param_grads needs to be 'torch' or 'fused', but {value!r} is given")
+        self._policy_param_grads = value
+
+    def vmap_policy_param_grads(self, policy, observations, grad_raw, obs_stepsize, action_stepsize, max_groups=0):
+        """The parameter gradient of a policy rollout on its own: sum over the batch and the action rows of (d mlp / d params)(obs
+        row)^T grad_raw row, flat like `policy.params` (in the environment's dtype on its device). One excenv_policy_param_grad call
+        (include/excenv.h): policy_param_grad_kernel on the matrix cores and a deterministic fp64 sum, no torch contraction.
+
+        observations [B, N+1, OW]: what `vmap_sim_ahead_policy` / `vmap_rollout_episodes` returned; the rows of the action rows are
+        read. grad_raw [B, K, A]: the `g_noise` of `vmap_sim_ahead_policy_vjp` (it already carries an episode mask). Lane-major views
+        are read in place, anything else is copied once. max_groups: 0 (auto), or at most this many workgroups — the grouping, and
+        with it the bits, are a function of (B, K, max_groups) only."""
+        from ._policy import MLPPolicy
+
+        assert isinstance(policy, MLPPolicy), f"policy needs to be an MLPPolicy, but {type(policy).__name__} is given"
+        if not (isinstance(max_groups, int) and max_groups >= 0):
+            raise ValueError(f"vmap_policy_param_grads: max_groups needs to be a non-negative integer (0: auto), but {max_groups!r} is given")
+        B, dt, dev = self.batch_size, self.dtype, self.device
+        sB = B or 1
+        OW, A = policy.widths[0], policy.widths[-1]
+        grad_raw = torch.as_tensor(grad_raw)
+        if not (grad_raw.ndim == 3 and grad_raw.shape[0] == B and grad_raw.shape[2] == A):
+            raise ValueError(f"vmap_policy_param_grads: grad_raw needs to be of shape (batch_size, n_actions, {A}), but "
+                             f"{tuple(grad_raw.shape)} is given")
+        K = grad_raw.shape[1]
+        sub = self._n_substeps(K, obs_stepsize, action_stepsize)
+        rows = K * sub + 1
+        observations = torch.as_tensor(observations)
+        if tuple(observations.shape) != (B, rows, OW):
+            raise ValueError(f"vmap_policy_param_grads: observations need to be of shape {(B, rows, OW)}, but "
+                             f"{tuple(observations.shape)} is given")
+        obs = cotangent(observations, dev, dt, (B, rows, OW), (1, OW * sB, sB))
+        g_raw = cotangent(grad_raw, dev, dt, (B, K, A), (1, A * sB, sB))
+        return self._policy_param_grad_launch(policy, policy.on(dev, dt).detach(), obs, g_raw, K, sub, max_groups)
+
+    def _policy_param_grad_launch(self, policy, params, obs, g_raw, K, sub, max_groups):
+        """One excenv_policy_param_grad call on lane-major obs ([N+1][OW][B] in memory) and g_raw ([K][A][B] in memory) -> flat
+        gradient like `params`. The workspace comes from a cache of this environment, keyed by its byte count."""
+        B, dt = self.batch_size, self.dtype
+        if B == 0:
+            return torch.zeros_like(params)
+        out = torch.empty_like(params)
+        widths = (ctypes.c_int32 * (_native.POLICY_MAX_LAYERS + 1))(*policy.widths)
+        record = _native.Policy(params.data_ptr(), policy.n_layers, _native.ACTIVATIONS[policy.activation], widths, None, 0.0, 0.0)
+        need = _native.lib().excenv_policy_param_grad_workspace_bytes(_native.dtype_id(dt), B, K, ctypes.byref(record), max_groups)
+        if need < 0:
+            raise ValueError(f"vmap_policy_param_grads: no workspace size for widths {policy.widths} and max_groups {max_groups}")
+        cache = self.__dict__.setdefault("_policy_param_grad_workspaces", {})
+        ws = cache.get(need)
+        if ws is None or ws.device != params.device:
+            ws = cache[need] = torch.empty(max(need // 8, 1), dtype=torch.float64, device=params.device)
+        call = _native.PolicyParamGrad(record, obs.data_ptr(), g_raw.data_ptr() if K > 0 else None, out.data_ptr(), ws.data_ptr(),
+                                       ws.numel() * 8, max_groups)
+        _native._launch("excenv_policy_param_grad", out, "vmap_policy_param_grads", _native.dtype_id(dt), B, K, sub, ctypes.byref(call))
+        return out
 
     def _policy_differentiable(self, init_state, policy, n_actions, obs_stepsize, action_stepsize, noise, clip):
         """vmap_sim_ahead_policy(differentiable=True) with an input that requires grad: records one autograd node."""
@@ -112,7 +191,9 @@ class PolicyVjpMixin:
         which is the noise's gradient whether or not a noise was given. g_params: flat like `policy.params` (in the environment's
         dtype on its device), summed over the batch and the action rows — `torch.autograd.grad(policy.torch_forward(rows), params,
         g_noise)` over the observation rows of the action rows, accumulated in chunks of at most 2^21 samples; None with
-        `param_grads=False` (the launch alone). The weights on reference columns do get gradients.
+        `param_grads=False` (the launch alone). `param_grads="torch"` is `True`; `param_grads="fused"` computes g_params with one
+        excenv_policy_param_grad call instead (`vmap_policy_param_grads`: the matrix cores, a deterministic fp64 sum; g_state0 and
+        g_noise keep their bits). Any other value raises a ValueError. The weights on reference columns do get gradients.
 
         reset [B, K] bool: the episode mask `vmap_rollout_episodes` returned (one solver step per action). Where reset[:, n] is set,
         step n -> n + 1 was a reset: nothing flows from row n + 1 back to row n, reset states get no gradient, and the action of row
@@ -122,6 +203,7 @@ class PolicyVjpMixin:
         from ._policy import MLPPolicy
 
         assert isinstance(policy, MLPPolicy), f"policy needs to be an MLPPolicy, but {type(policy).__name__} is given"
+        _param_grad_route(param_grads)  # (refused by name before anything else)
         why = self._feedback_vjp_unsupported()
         if why is not None:
             raise ValueError(f"vmap_sim_ahead_policy_vjp: {why}")
@@ -137,7 +219,9 @@ class PolicyVjpMixin:
     def _policy_vjp_launch(self, policy, obs, traj, actions, obs_stepsize, action_stepsize, clip, g_obs, g_states, g_last, g_actions,
                            reset, param_grads, packed=None):
         """-> ([grad of the initial state leaves], g_noise [B, K, A], g_params flat or None): one excenv_sim_policy_vjp call and the
-        parameter contraction in torch. packed: the forward's packed properties."""
+        parameter contraction, in torch or in one excenv_policy_param_grad call (`param_grads`: PARAM_GRAD_ROUTES). packed: the
+        forward's packed properties."""
+        route = _param_grad_route(param_grads)
         B, S, A, OW = self.batch_size, self.physical_state_dim, self.action_dim, self._obs_dim()
         dt, dev = self.dtype, self.device
         sB = B or 1
@@ -194,7 +278,9 @@ class PolicyVjpMixin:
             self.last_policy_vjp_launch = _native.last_launch()
         g_noise = g_raw.permute(2, 0, 1)
         g_params = None
-        if param_grads:
+        if route == "fused":
+            g_params = self._policy_param_grad_launch(policy, params, obs, g_raw, K, sub, 0)
+        elif route == "torch":
             g_params = torch.zeros_like(params)
             if B > 0 and K > 0:
                 rows_k = obs[:, 0:K * sub:sub, :]  # [B, K, OW]: the observation rows of the action rows

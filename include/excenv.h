@@ -706,6 +706,49 @@ int excenv_sim_policy_vjp(int env, int solver, int dtype, int64_t B, int64_t K, 
                           const excenv_control_t* control, double obs_stepsize, double env_tau, const excenv_policy_vjp_t* call,
                           const excenv_launch_opts_t* opts, void* stream);
 
+/* ---- the parameter gradient of a policy rollout: the contraction excenv_sim_policy_vjp leaves to its caller, on the matrix cores
+ * (additions, same ABI version: a binder probes for the symbols). It needs no environment, solver or properties, only the network
+ * and two lane-major arrays:
+ *   grad_params = sum over b < B, k < K of (d mlp / d params)(obs_traj[k * substeps][.][b])^T grad_raw[k][.][b]
+ * with mlp the network of excenv_sim_policy and the derivative conventions of excenv_sim_policy_vjp: the hidden layers are evaluated
+ * again (bias first, then the inputs in ascending order); EXCENV_ACT_RELU passes where the recomputed activation h > 0 and gives 0
+ * elsewhere, EXCENV_ACT_TANH multiplies by 1 - h * h. All OW columns are read: the weights on reference columns get gradients. An
+ * episode mask needs no handling: grad_raw already carries it.
+ * Two launches on `stream`: policy_param_grad_kernel, then policy_param_grad_reduce_kernel. A sample tile is 64 consecutive
+ * environments of one action row, tile number k * ceil(B / 64) + b_tile; with T tiles and G = min(T, max_groups > 0 ? max_groups :
+ * EXCENV_PARAM_GRAD_AUTO_GROUPS) workgroups, workgroup g owns the tiles first(g) .. first(g + 1) - 1, first(g) = g * (T / G) +
+ * min(g, T mod G): a function of (B, K, max_groups) only, never of the device, so the same call gives the same bits on every run. A
+ * workgroup sums at most
+ * EXCENV_PARAM_GRAD_CHAIN samples in the working dtype (v_mfma_*_16x16x4 accumulators: a k-ordered fused multiply-add chain) before
+ * it adds them into its own fp64 slot of the workspace; the second launch adds the G slots of every parameter in ascending order in
+ * fp64 and stores the working dtype. No atomics.
+ *   policy      : params, n_layers, activation and widths of the forward; noise and the clip bounds are not read. widths[0] = OW is
+ *                 1 .. EXCENV_POLICY_MAX_INPUT, widths[n_layers] = A is 1 .. EXCENV_MAX_ACTION
+ *   obs_traj    : [K * substeps + 1][OW][B]: rows k * substeps are read;  grad_raw: [K][A][B], what excenv_sim_policy_vjp wrote
+ *   grad_params : (out) [policy parameter count] of the working dtype, laid out like params: W_1, b_1, .., W_L, b_L
+ *   workspace   : excenv_policy_param_grad_workspace_bytes(dtype, B, K, &policy, max_groups) bytes of device memory (G * parameter
+ *                 count * 8; -1 for a bad argument), 8-byte aligned; needs no initialisation
+ * Never allocates or synchronises. B == 0 returns EXCENV_OK without a launch; K == 0 with B > 0 writes zeros (the second launch
+ * alone, over zero slots). excenv_last_launch() reports "policy_param_grad_kernel". Validated before any HIP call: EXCENV_ENULL names
+ * a missing pointer (call, policy.params, obs_traj, grad_raw with K > 0, grad_params, workspace); EXCENV_EINVAL: dtype, B < 0, K < 0,
+ * substeps < 1, K * substeps >= 2^31, n_layers outside 1 .. 4, a hidden width outside 1 .. 64, widths[0] outside 1 .. 16,
+ * widths[n_layers] outside 1 .. 2, an unknown activation, max_groups < 0, a workspace that is too small or misaligned (with the
+ * byte count). */
+#define EXCENV_POLICY_MAX_INPUT 16        /* the widest observation row: 8 + EXCENV_MAX_CONTROL */
+#define EXCENV_PARAM_GRAD_CHAIN 4096      /* samples one working-dtype accumulator sums before it goes to fp64 */
+#define EXCENV_PARAM_GRAD_AUTO_GROUPS 512 /* workgroups of max_groups == 0, at most */
+typedef struct {
+  excenv_policy_t policy;   /* params, n_layers, activation, widths of the forward; noise and clip bounds are not read */
+  const void* obs_traj;     /* [K * substeps + 1][OW][B], OW = widths[0]: rows k * substeps are read, all OW columns */
+  const void* grad_raw;     /* [K][A][B], A = widths[n_layers]: what excenv_sim_policy_vjp wrote */
+  void* grad_params;        /* (out) [policy parameter count] of the working dtype, laid out like params */
+  void* workspace;          /* excenv_policy_param_grad_workspace_bytes bytes of device memory, 8-byte aligned; no initialisation */
+  int64_t workspace_bytes;
+  int32_t max_groups;       /* 0: auto; > 0: at most this many workgroups (tests, reproducibility across shapes) */
+} excenv_policy_param_grad_t;
+int64_t excenv_policy_param_grad_workspace_bytes(int dtype, int64_t B, int64_t K, const excenv_policy_t* policy, int32_t max_groups);
+int excenv_policy_param_grad(int dtype, int64_t B, int64_t K, int32_t substeps, const excenv_policy_param_grad_t* call, void* stream);
+
 /* ---- replaces CoreEnvironment.vmap_generate_state_from_observation (core_env.py:689-705; per env e.g.
  * pendulum_env.py:331-364, pmsm_env.py:921-970): obs [B][O + n_control] row-major -> denormalised physical state leaves
  * state_out[S][B] and, for each controlled field control_idx[j], its denormalised reference leaf reference_out[j][B]

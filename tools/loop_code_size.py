@@ -4,7 +4,7 @@ the headline loop (PMSM Euler fp32, V = 4, ping-pong: two unrolled solver steps 
 any growth — gym outputs on the vector path, a third register set — would fall off that cliff unnoticed (misses are < 1e-5
 today, tools/icache_probe.sh). This tool takes the device code out of the built library, disassembles every
 sim_ahead_kernel / sim_ahead_em_kernel (loop_spans(match=...): any other family, "sim_feedback_kernel", "sim_policy_kernel",
-"sim_episodes_kernel", "sim_policy_vjp_kernel") and
+"sim_episodes_kernel", "sim_policy_vjp_kernel", "policy_param_grad_kernel", "policy_param_grad_reduce_kernel") and
 reports the span of its largest backward branch = the outermost loop — or more: where
 the compiler has moved a cold block behind the loop (the once-per-launch vote of EXCENV_OPT_KEEP_CONSTANT_COLUMNS in the PMSM lean
 kernels) the way back from it is a backward branch across the whole loop, and the figure is then loop + everything up to that block
