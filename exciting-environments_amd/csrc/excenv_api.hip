@@ -24,6 +24,8 @@ void set_error(const char* fmt, ...) {
 int launch_transpose(int dtype, int64_t M, int64_t N, const void* in, void* out, hipStream_t stream);
 int launch_param_sum(int dtype, int64_t B, int n, const void* const* per_env, void* out, void* workspace, hipStream_t stream);
 int launch_policy_param_grad(int dtype, int64_t B, int64_t K, int32_t substeps, const excenv_policy_param_grad_t& call, hipStream_t stream);
+int launch_policy_eval(int dtype, int64_t B, int64_t R, int64_t row_stride, const excenv_policy_eval_t& call, hipStream_t stream);
+int launch_gae(int dtype, int64_t B, int64_t K, const excenv_gae_t& call, hipStream_t stream);
 
 EnvVTable vtable_pendulum();
 EnvVTable vtable_msd();
@@ -851,6 +853,24 @@ int excenv_policy_param_grad(int dtype, int64_t B, int64_t K, int32_t substeps, 
   }
   if (B == 0) return EXCENV_OK;
   return launch_policy_param_grad(dtype, B, K, substeps, *call, (hipStream_t)stream);
+}
+
+int excenv_policy_eval(int dtype, int64_t B, int64_t R, int64_t row_stride, const excenv_policy_eval_t* call, void* stream) {
+  {
+    char why[256];
+    if (int rc = policy_eval_refusal(dtype, B, R, row_stride, call, why, sizeof(why))) { set_error("%s", why); return rc; }
+  }
+  if (B == 0 || R == 0) return EXCENV_OK;
+  return launch_policy_eval(dtype, B, R, row_stride, *call, (hipStream_t)stream);
+}
+
+int excenv_gae(int dtype, int64_t B, int64_t K, const excenv_gae_t* call, void* stream) {
+  {
+    char why[256];
+    if (int rc = gae_refusal(dtype, B, K, call, why, sizeof(why))) { set_error("%s", why); return rc; }
+  }
+  if (B == 0 || K == 0) return EXCENV_OK;
+  return launch_gae(dtype, B, K, *call, (hipStream_t)stream);
 }
 
 int excenv_state_from_observation(int env, int dtype, int64_t B, const excenv_props_t* props, int32_t n_control,

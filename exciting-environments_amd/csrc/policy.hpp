@@ -4,7 +4,8 @@
 // record, what the entry point refuses about that record, the name of sim_episodes_kernel (kernels_policy_episodes.hpp). Last the
 // reverse mode, excenv_sim_policy_vjp: its call, its LDS and bytes, its refusals and the name of sim_policy_vjp_kernel
 // (kernels_policy_vjp.hpp), and the parameter gradient, excenv_policy_param_grad: its tiles, workgroups, LDS, workspace and refusals
-// (policy_param_grad.hip).
+// (policy_param_grad.hip). Behind them the update step on stored rows: excenv_policy_eval (policy_eval.hip: tiles, workgroups, LDS,
+// refusals) and excenv_gae (gae.hip: block, prefetch depth, refusals).
 #pragma once
 #include "closed_loop_call.hpp"
 
@@ -258,6 +259,117 @@ inline int policy_param_grad_refusal(int dtype, int64_t B, int64_t K, int32_t su
   const int64_t need = policy_param_grad_workspace(B, K, p, c->max_groups);
   if (c->workspace_bytes < need || (reinterpret_cast<uintptr_t>(c->workspace) & 7u) != 0) {
     std::snprintf(msg, n, "%s: needs an 8-byte aligned workspace of %lld bytes (excenv_policy_param_grad_workspace_bytes)", fn, (long long)need);
+    return EXCENV_EINVAL;
+  }
+  return EXCENV_OK;
+}
+
+// ---- the network on stored rows: excenv_policy_eval ----------------------------------------------------------------
+// policy_eval_kernel<T> (policy_eval.hip): no model, one instantiation per type
+constexpr const char* policy_eval_name() { return "policy_eval_kernel"; }
+
+// Whether the fp64 instantiation multiplies on the matrix cores (v_mfma_f64_16x16x4_f64) or by per-lane fma chains; the fp32 one
+// always uses v_mfma_f32_16x16x4_f32. The contract is the bits of the chain either way (DESIGN.md §4.17 says which form shipped).
+constexpr bool POLICY_EVAL_F64_MMA = true;
+// Workgroups of a launch at the most: eight for each of the 256 compute units
+constexpr int POLICY_EVAL_MAX_GROUPS = 2048;
+
+// The rows of the tile in LDS, PARAM_GRAD_LDS_STRIDE elements each: x^0 twice (the next tile is staged while this one is read), then
+// two buffers the hidden layers alternate between: x^1 and x^3 in the first, x^2 in the second
+inline int policy_eval_lds_rows(const excenv_policy_t& p) {
+  const int L = p.n_layers;
+  const int h1 = L >= 2 ? p.widths[1] : 0, h2 = L >= 3 ? p.widths[2] : 0, h3 = L >= 4 ? p.widths[3] : 0;
+  return 2 * p.widths[0] + (h1 > h3 ? h1 : h3) + h2;
+}
+inline size_t policy_eval_lds_bytes(const excenv_policy_t& p, size_t elem) {
+  return (size_t)policy_eval_lds_rows(p) * PARAM_GRAD_LDS_STRIDE * elem;
+}
+
+// Sample tiles of a call (64 consecutive environments of one evaluated row, tile number r * ceil(B / 64) + b_tile) and its workgroups;
+// workgroup g owns the tiles policy_param_grad_first_tile(tiles, groups, g) .. (g + 1) - 1: functions of (B, R) only
+inline int64_t policy_eval_tiles(int64_t B, int64_t R) { return R * ((B + PARAM_GRAD_TILE - 1) / PARAM_GRAD_TILE); }
+inline int64_t policy_eval_groups(int64_t B, int64_t R) {
+  const int64_t tiles = policy_eval_tiles(B, R);
+  return tiles < POLICY_EVAL_MAX_GROUPS ? tiles : POLICY_EVAL_MAX_GROUPS;
+}
+
+// What excenv_policy_eval refuses: EXCENV_OK, or the code with the message in `msg`. NULL pointers first, then values.
+inline int policy_eval_refusal(int dtype, int64_t B, int64_t R, int64_t row_stride, const excenv_policy_eval_t* c, char* msg, size_t n) {
+  const char* fn = "excenv_policy_eval";
+  auto null = [&](const char* what) { std::snprintf(msg, n, "%s: %s is NULL", fn, what); return EXCENV_ENULL; };
+  if (!c) return null("call");
+  const excenv_policy_t& p = c->policy;
+  if (!p.params) return null("call->policy.params");
+  if (!c->obs_traj) return null("call->obs_traj");
+  if (!c->out) return null("call->out");
+  if (dtype != EXCENV_F32 && dtype != EXCENV_F64) {
+    std::snprintf(msg, n, "%s: dtype must be EXCENV_F32 (0) or EXCENV_F64 (1) (got %d)", fn, dtype);
+    return EXCENV_EINVAL;
+  }
+  if (B < 0 || R < 0 || row_stride < 1) {
+    std::snprintf(msg, n, "%s: bad B=%lld, R=%lld or row_stride=%lld", fn, (long long)B, (long long)R, (long long)row_stride);
+    return EXCENV_EINVAL;
+  }
+  if (R > 1 && row_stride > (int64_t)0x7fffffff / (R - 1)) {
+    std::snprintf(msg, n, "%s: (R - 1) * row_stride = %lld * %lld rows exceed one launch", fn, (long long)(R - 1), (long long)row_stride);
+    return EXCENV_EINVAL;
+  }
+  if (p.n_layers < 1 || p.n_layers > EXCENV_POLICY_MAX_LAYERS) {
+    std::snprintf(msg, n, "%s: policy.n_layers must be 1 .. %d (got %d)", fn, EXCENV_POLICY_MAX_LAYERS, p.n_layers);
+    return EXCENV_EINVAL;
+  }
+  for (int l = 1; l < p.n_layers; ++l) {
+    if (p.widths[l] < 1 || p.widths[l] > EXCENV_POLICY_MAX_WIDTH) {
+      std::snprintf(msg, n, "%s: policy.widths[%d] must be 1 .. %d (got %d)", fn, l, EXCENV_POLICY_MAX_WIDTH, p.widths[l]);
+      return EXCENV_EINVAL;
+    }
+  }
+  if (p.widths[0] < 1 || p.widths[0] > EXCENV_POLICY_MAX_INPUT) {
+    std::snprintf(msg, n, "%s: policy.widths[0] must be 1 .. %d (the widest observation row; got %d)", fn, EXCENV_POLICY_MAX_INPUT, p.widths[0]);
+    return EXCENV_EINVAL;
+  }
+  if (p.widths[p.n_layers] < 1 || p.widths[p.n_layers] > EXCENV_MAX_ACTION) {
+    std::snprintf(msg, n, "%s: policy.widths[%d] must be 1 .. %d (the action width; got %d)", fn, p.n_layers, EXCENV_MAX_ACTION,
+                  p.widths[p.n_layers]);
+    return EXCENV_EINVAL;
+  }
+  if (p.activation != EXCENV_ACT_RELU && p.activation != EXCENV_ACT_TANH) {
+    std::snprintf(msg, n, "%s: policy.activation must be EXCENV_ACT_RELU (0) or EXCENV_ACT_TANH (1) (got %d)", fn, p.activation);
+    return EXCENV_EINVAL;
+  }
+  return EXCENV_OK;
+}
+
+// ---- generalised advantage estimation on lane-major rows: excenv_gae ----------------------------------------------
+// gae_kernel<T> (gae.hip): one environment per lane, one instantiation per type
+constexpr const char* gae_name() { return "gae_kernel"; }
+constexpr int GAE_BLOCK = 256;
+// Rows of loads a lane keeps in flight ahead of the scan (the loads of row n do not depend on the carry)
+constexpr int GAE_DEPTH = 8;
+
+// What excenv_gae refuses: EXCENV_OK, or the code with the message in `msg`. NULL pointers first, then values. A NaN fails both
+// comparisons of its range.
+inline int gae_refusal(int dtype, int64_t B, int64_t K, const excenv_gae_t* c, char* msg, size_t n) {
+  const char* fn = "excenv_gae";
+  auto null = [&](const char* what) { std::snprintf(msg, n, "%s: %s is NULL", fn, what); return EXCENV_ENULL; };
+  if (!c) return null("call");
+  if (!c->reward) return null("call->reward");
+  if (!c->value) return null("call->value");
+  if (!c->advantage) return null("call->advantage");
+  if (dtype != EXCENV_F32 && dtype != EXCENV_F64) {
+    std::snprintf(msg, n, "%s: dtype must be EXCENV_F32 (0) or EXCENV_F64 (1) (got %d)", fn, dtype);
+    return EXCENV_EINVAL;
+  }
+  if (B < 0 || K < 0) {
+    std::snprintf(msg, n, "%s: bad B=%lld or K=%lld", fn, (long long)B, (long long)K);
+    return EXCENV_EINVAL;
+  }
+  if (!(c->gamma >= 0.0 && c->gamma <= 1.0)) {
+    std::snprintf(msg, n, "%s: call->gamma must lie in [0, 1] (got %g)", fn, c->gamma);
+    return EXCENV_EINVAL;
+  }
+  if (!(c->lambda >= 0.0 && c->lambda <= 1.0)) {
+    std::snprintf(msg, n, "%s: call->lambda must lie in [0, 1] (got %g)", fn, c->lambda);
     return EXCENV_EINVAL;
   }
   return EXCENV_OK;

@@ -132,6 +132,19 @@ class PolicyParamGrad(ctypes.Structure):
                 ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_int64), ("max_groups", ctypes.c_int32)]
 
 
+class PolicyEval(ctypes.Structure):
+    """excenv_policy_eval_t: the network, the stored observation rows and where its raw outputs go (excenv_policy_eval)."""
+
+    _fields_ = [("policy", Policy), ("obs_traj", ctypes.c_void_p), ("out", ctypes.c_void_p)]
+
+
+class Gae(ctypes.Structure):
+    """excenv_gae_t: lane-major reward / value rows, the optional flag bytes, the two discounts and the outputs (excenv_gae)."""
+
+    _fields_ = [("reward", ctypes.c_void_p), ("value", ctypes.c_void_p), ("terminated", ctypes.c_void_p), ("reset", ctypes.c_void_p),
+                ("gamma", ctypes.c_double), ("lambda", ctypes.c_double), ("advantage", ctypes.c_void_p), ("returns", ctypes.c_void_p)]
+
+
 class Episode(ctypes.Structure):
     """excenv_episode_t: the reset rows, the end conditions and the gym / reset outputs of excenv_sim_policy_episodes."""
 
@@ -145,7 +158,8 @@ class Episode(ctypes.Structure):
 STRUCTS = {Param: "excenv_param_t", PmsmLut: "excenv_pmsm_lut_t", Props: "excenv_props_t", LaunchOpts: "excenv_launch_opts_t",
            TrajGym: "excenv_traj_gym_t", Control: "excenv_control_t", Feedback: "excenv_feedback_t",
            FeedbackVjp: "excenv_feedback_vjp_t", Policy: "excenv_policy_t", Episode: "excenv_episode_t",
-           PolicyVjp: "excenv_policy_vjp_t", PolicyParamGrad: "excenv_policy_param_grad_t"}
+           PolicyVjp: "excenv_policy_vjp_t", PolicyParamGrad: "excenv_policy_param_grad_t", PolicyEval: "excenv_policy_eval_t",
+           Gae: "excenv_gae_t"}
 
 _vp, _ci, _i32, _i64, _cd = ctypes.c_void_p, ctypes.c_int, ctypes.c_int32, ctypes.c_int64, ctypes.c_double
 _STEP = [_ci, _ci, _ci, _i64, _vp, _vp, _cd, _vp, _vp, _vp, _vp]  # env, solver, dtype, B, props, control, tau, in, action, out, obs
@@ -213,6 +227,10 @@ PROTOTYPES = {
     "excenv_policy_param_grad_workspace_bytes": (_i64, [_ci, _i64, _i64, _vp, _i32]),
     # dtype, B, K, substeps, call, stream
     "excenv_policy_param_grad": (_ci, [_ci, _i64, _i64, _i32, _vp, _vp]),
+    # dtype, B, R, row_stride, call, stream
+    "excenv_policy_eval": (_ci, [_ci, _i64, _i64, _i64, _vp, _vp]),
+    # dtype, B, K, call, stream
+    "excenv_gae": (_ci, [_ci, _i64, _i64, _vp, _vp]),
     "excenv_state_from_observation": (_ci, [_ci, _ci, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "excenv_update_ref": (_ci, [_ci, _ci, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
     "excenv_observe": (_ci, [_ci, _ci, _i64, _vp, _vp, _vp, _vp, _vp]),

@@ -749,6 +749,61 @@ typedef struct {
 int64_t excenv_policy_param_grad_workspace_bytes(int dtype, int64_t B, int64_t K, const excenv_policy_t* policy, int32_t max_groups);
 int excenv_policy_param_grad(int dtype, int64_t B, int64_t K, int32_t substeps, const excenv_policy_param_grad_t* call, void* stream);
 
+/* ---- the network of excenv_sim_policy on stored observation rows: the forward half beside
+ * excenv_policy_param_grad, for the new means and the critic's values of an on-policy update. Model-free, lane-major:
+ *   out[r][q][b] = x^L[q] of mlp(obs_traj[r * row_stride][.][b]),   r < R, q < A, b < B
+ * with mlp excenv_sim_policy's network exactly: every unit starts at its bias and adds the inputs in ascending order, one fused
+ * multiply-add each; EXCENV_ACT_RELU / EXCENV_ACT_TANH (the rollout's own functions) behind every layer but the last; no noise and no
+ * clamp. out[r] is bit for bit the x^L sim_policy_kernel / sim_episodes_kernel computed for the same stored row, in fp32 and fp64 (the
+ * stored row, reference columns included, is what the rollout's network read), so clamp(noise[k] + out[k]) reproduces actions_out[k].
+ * One launch of policy_eval_kernel on `stream`. A sample tile is 64 consecutive environments of one evaluated row, tile number
+ * r * ceil(B / 64) + b_tile; with T tiles and G = min(T, 2048) workgroups, workgroup g owns the tiles first(g) .. first(g + 1) - 1,
+ * first(g) = g * (T / G) + min(g, T mod G): a function of (B, R) only.
+ *   policy   : params, n_layers, activation and widths; noise and the clip bounds are not read. widths[0] = OW is
+ *              1 .. EXCENV_POLICY_MAX_INPUT, widths[n_layers] = A is 1 .. EXCENV_MAX_ACTION. A critic is a network with A = 1.
+ *   obs_traj : [(R - 1) * row_stride + 1 or more][OW][B]: rows r * row_stride are read, all OW columns
+ *   out      : (out) [R][A][B] of the working dtype
+ * Never allocates or synchronises. B == 0 or R == 0 returns EXCENV_OK without a launch. excenv_last_launch() reports
+ * "policy_eval_kernel". Validated before any HIP call: EXCENV_ENULL names a missing pointer (call, policy.params, obs_traj, out);
+ * EXCENV_EINVAL: dtype, B < 0, R < 0, row_stride < 1, (R - 1) * row_stride >= 2^31, n_layers outside 1 .. 4, a hidden width outside
+ * 1 .. 64, widths[0] outside 1 .. 16, widths[n_layers] outside 1 .. 2, an unknown activation. */
+typedef struct {
+  excenv_policy_t policy;   /* params, n_layers, activation, widths; noise and clip bounds are not read */
+  const void* obs_traj;     /* [(R - 1) * row_stride + 1 or more][OW][B], OW = widths[0]: rows r * row_stride are read */
+  void* out;                /* (out) [R][A][B], A = widths[n_layers] */
+} excenv_policy_eval_t;
+int excenv_policy_eval(int dtype, int64_t B, int64_t R, int64_t row_stride, const excenv_policy_eval_t* call, void* stream);
+
+/* ---- generalised advantage estimation on lane-major rows, in the convention of excenv_sim_policy_episodes:
+ * reward[n] and terminated[n] belong to row n + 1; reset[n] says that row n is a terminal observation and row n + 1 the first one of
+ * the next episode, so n -> n + 1 is no transition. An episode cut by `truncated` or by the step budget at row n + 1 has reset[n + 1]
+ * set and bootstraps from value[n + 1], the terminal observation; a terminated episode does not bootstrap; row K bootstraps the
+ * running episode. Arithmetic in the working dtype T with g = (T)gamma and gl = (T)(g * (T)lambda). Per environment, carry = 0; for
+ * n = K - 1 down to 0:
+ *   if reset[n]:  advantage[n] = 0;  returns[n] = value[n];  carry = 0      (not a transition: row n + 1 is a reset state)
+ *   else:
+ *       nt    = !terminated[n]
+ *       boot  = nt ? value[n + 1] : 0                    (a select, not a product: a NaN behind a terminal row does not leak)
+ *       delta = fma(g, boot, reward[n]) - value[n]
+ *       carry = nt ? fma(gl, carry, delta) : delta
+ *       advantage[n] = carry;  returns[n] = carry + value[n]
+ * One launch of gae_kernel on `stream`, one environment per lane; the same call gives the same bits on every run.
+ *   reward [K][B], value [K + 1][B] of the working dtype;  terminated, reset: [K][B] bytes (non-zero: set) at any byte offset, or NULL
+ *   for never;  advantage: (out) [K][B];  returns: (out) [K][B] or NULL
+ * Never allocates or synchronises. B == 0 or K == 0 returns EXCENV_OK without a launch. excenv_last_launch() reports "gae_kernel".
+ * Validated before any HIP call: EXCENV_ENULL names a missing pointer (call, reward, value, advantage); EXCENV_EINVAL: dtype, B < 0,
+ * K < 0, a gamma or lambda that is NaN or outside [0, 1]. */
+typedef struct {
+  const void* reward;         /* [K][B] */
+  const void* value;          /* [K + 1][B] */
+  const uint8_t* terminated;  /* [K][B] bytes or NULL (never) */
+  const uint8_t* reset;       /* [K][B] bytes or NULL (never) */
+  double gamma, lambda;       /* both in [0, 1] */
+  void* advantage;            /* (out) [K][B] */
+  void* returns;              /* (out) [K][B] or NULL */
+} excenv_gae_t;
+int excenv_gae(int dtype, int64_t B, int64_t K, const excenv_gae_t* call, void* stream);
+
 /* ---- replaces CoreEnvironment.vmap_generate_state_from_observation (core_env.py:689-705; per env e.g.
  * pendulum_env.py:331-364, pmsm_env.py:921-970): obs [B][O + n_control] row-major -> denormalised physical state leaves
  * state_out[S][B] and, for each controlled field control_idx[j], its denormalised reference leaf reference_out[j][B]
