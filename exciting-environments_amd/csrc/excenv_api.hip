@@ -26,6 +26,8 @@ int launch_param_sum(int dtype, int64_t B, int n, const void* const* per_env, vo
 int launch_policy_param_grad(int dtype, int64_t B, int64_t K, int32_t substeps, const excenv_policy_param_grad_t& call, hipStream_t stream);
 int launch_policy_eval(int dtype, int64_t B, int64_t R, int64_t row_stride, const excenv_policy_eval_t& call, hipStream_t stream);
 int launch_gae(int dtype, int64_t B, int64_t K, const excenv_gae_t& call, hipStream_t stream);
+int launch_gaussian_logp(int dtype, int64_t B, int64_t K, const excenv_gaussian_logp_t& call, hipStream_t stream);
+int launch_ppo_loss(bool grad, int dtype, int64_t B, int64_t K, const excenv_ppo_loss_t& call, hipStream_t stream);
 
 EnvVTable vtable_pendulum();
 EnvVTable vtable_msd();
@@ -871,6 +873,38 @@ int excenv_gae(int dtype, int64_t B, int64_t K, const excenv_gae_t* call, void* 
   }
   if (B == 0 || K == 0) return EXCENV_OK;
   return launch_gae(dtype, B, K, *call, (hipStream_t)stream);
+}
+
+int excenv_gaussian_logp(int dtype, int64_t B, int64_t K, const excenv_gaussian_logp_t* call, void* stream) {
+  {
+    char why[256];
+    if (int rc = gaussian_logp_refusal(dtype, B, K, call, why, sizeof(why))) { set_error("%s", why); return rc; }
+  }
+  if (B == 0 || K == 0) return EXCENV_OK;
+  return launch_gaussian_logp(dtype, B, K, *call, (hipStream_t)stream);
+}
+
+int64_t excenv_ppo_loss_workspace_bytes(int64_t B, int64_t K, int32_t max_groups) {
+  if (B < 0 || K < 0 || max_groups < 0) return -1;
+  return ppo_loss_workspace(B, K, max_groups);
+}
+
+int excenv_ppo_loss(int dtype, int64_t B, int64_t K, const excenv_ppo_loss_t* call, void* stream) {
+  {
+    char why[256];
+    if (int rc = ppo_loss_refusal(false, dtype, B, K, call, why, sizeof(why))) { set_error("%s", why); return rc; }
+  }
+  if (B == 0 || K == 0) return EXCENV_OK;
+  return launch_ppo_loss(false, dtype, B, K, *call, (hipStream_t)stream);
+}
+
+int excenv_ppo_loss_grad(int dtype, int64_t B, int64_t K, const excenv_ppo_loss_t* call, void* stream) {
+  {
+    char why[256];
+    if (int rc = ppo_loss_refusal(true, dtype, B, K, call, why, sizeof(why))) { set_error("%s", why); return rc; }
+  }
+  if (B == 0 || K == 0) return EXCENV_OK;
+  return launch_ppo_loss(true, dtype, B, K, *call, (hipStream_t)stream);
 }
 
 int excenv_state_from_observation(int env, int dtype, int64_t B, const excenv_props_t* props, int32_t n_control,

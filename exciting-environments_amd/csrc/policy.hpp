@@ -5,7 +5,8 @@
 // reverse mode, excenv_sim_policy_vjp: its call, its LDS and bytes, its refusals and the name of sim_policy_vjp_kernel
 // (kernels_policy_vjp.hpp), and the parameter gradient, excenv_policy_param_grad: its tiles, workgroups, LDS, workspace and refusals
 // (policy_param_grad.hip). Behind them the update step on stored rows: excenv_policy_eval (policy_eval.hip: tiles, workgroups, LDS,
-// refusals) and excenv_gae (gae.hip: block, prefetch depth, refusals).
+// refusals), excenv_gae (gae.hip: block, prefetch depth, refusals) and the PPO objective, excenv_gaussian_logp / excenv_ppo_loss /
+// excenv_ppo_loss_grad (ppo_loss.hip: tiles, workgroups, workspace, refusals).
 #pragma once
 #include "closed_loop_call.hpp"
 
@@ -373,6 +374,108 @@ inline int gae_refusal(int dtype, int64_t B, int64_t K, const excenv_gae_t* c, c
     return EXCENV_EINVAL;
   }
   return EXCENV_OK;
+}
+
+// ---- the clipped PPO objective on lane-major rows: excenv_gaussian_logp, excenv_ppo_loss, excenv_ppo_loss_grad -----
+// gaussian_logp_kernel<T, A>, ppo_loss_kernel<T, A>, ppo_loss_grad_kernel<T, A> and ppo_loss_reduce_kernel (ppo_loss.hip): no model,
+// one instantiation per type and action width
+constexpr const char* gaussian_logp_name() { return "gaussian_logp_kernel"; }
+constexpr const char* ppo_loss_name() { return "ppo_loss_kernel"; }
+constexpr const char* ppo_loss_grad_name() { return "ppo_loss_grad_kernel"; }
+constexpr int PPO_BLOCK = 256;                           // four waves
+constexpr int PPO_LANE = EXCENV_PPO_TILE / PPO_BLOCK;    // consecutive samples of a lane: 16 bytes of fp32
+static_assert(PPO_LANE == 4, "a lane's samples are one 16-byte access in fp32, two in fp64");
+constexpr int PPO_SLOTS = EXCENV_PPO_STATS + EXCENV_MAX_ACTION;  // fp64 sums of one partial set
+
+// Sample tiles of a call (EXCENV_PPO_TILE consecutive environments of one row, tile number n * ceil(B / EXCENV_PPO_TILE) + b_tile) and
+// its workgroups; workgroup g owns the tiles policy_param_grad_first_tile(tiles, groups, g) .. (g + 1) - 1: functions of
+// (B, K, max_groups) only
+inline int64_t ppo_tiles(int64_t B, int64_t K) { return K * ((B + EXCENV_PPO_TILE - 1) / EXCENV_PPO_TILE); }
+inline int64_t ppo_groups(int64_t B, int64_t K, int32_t max_groups) {
+  const int64_t tiles = ppo_tiles(B, K), cap = max_groups > 0 ? max_groups : EXCENV_PPO_AUTO_GROUPS;
+  return tiles < cap ? tiles : cap;
+}
+inline int64_t ppo_loss_workspace(int64_t B, int64_t K, int32_t max_groups) { return ppo_groups(B, K, max_groups) * PPO_SLOTS * 8; }
+
+// What the three entries refuse: EXCENV_OK, or the code with the message in `msg`. NULL pointers first, then values. A NaN fails both
+// comparisons of clip_eps' range.
+inline int ppo_common_refusal(const char* fn, int n_actions, int dtype, int64_t B, int64_t K, char* msg, size_t n) {
+  if (n_actions < 1 || n_actions > EXCENV_MAX_ACTION) {
+    std::snprintf(msg, n, "%s: call->n_actions must be 1 .. %d (got %d)", fn, EXCENV_MAX_ACTION, n_actions);
+    return EXCENV_EINVAL;
+  }
+  if (dtype != EXCENV_F32 && dtype != EXCENV_F64) {
+    std::snprintf(msg, n, "%s: dtype must be EXCENV_F32 (0) or EXCENV_F64 (1) (got %d)", fn, dtype);
+    return EXCENV_EINVAL;
+  }
+  if (B < 0 || K < 0) {
+    std::snprintf(msg, n, "%s: bad B=%lld or K=%lld", fn, (long long)B, (long long)K);
+    return EXCENV_EINVAL;
+  }
+  return EXCENV_OK;
+}
+inline int ppo_rows_refusal(const char* fn, int n_actions, int64_t K, char* msg, size_t n) {
+  if (K > (int64_t)0x7fffffff / n_actions) {
+    std::snprintf(msg, n, "%s: K * n_actions = %lld * %d rows exceed one launch", fn, (long long)K, n_actions);
+    return EXCENV_EINVAL;
+  }
+  return EXCENV_OK;
+}
+inline int gaussian_logp_refusal(int dtype, int64_t B, int64_t K, const excenv_gaussian_logp_t* c, char* msg, size_t n) {
+  const char* fn = "excenv_gaussian_logp";
+  auto null = [&](const char* what) { std::snprintf(msg, n, "%s: %s is NULL", fn, what); return EXCENV_ENULL; };
+  if (!c) return null("call");
+  if (!c->mean) return null("call->mean");
+  if (!c->sample) return null("call->sample");
+  if (!c->inv_std) return null("call->inv_std");
+  if (!c->logp_const) return null("call->logp_const");
+  if (!c->logp) return null("call->logp");
+  if (int rc = ppo_common_refusal(fn, c->n_actions, dtype, B, K, msg, n)) return rc;
+  return ppo_rows_refusal(fn, c->n_actions, K, msg, n);
+}
+// grad: excenv_ppo_loss_grad (grad_scale and an output instead of stats and the workspace)
+inline int ppo_loss_refusal(bool grad, int dtype, int64_t B, int64_t K, const excenv_ppo_loss_t* c, char* msg, size_t n) {
+  const char* fn = grad ? "excenv_ppo_loss_grad" : "excenv_ppo_loss";
+  auto null = [&](const char* what) { std::snprintf(msg, n, "%s: %s is NULL", fn, what); return EXCENV_ENULL; };
+  if (!c) return null("call");
+  if (!c->mean) return null("call->mean");
+  if (!c->sample) return null("call->sample");
+  if (!c->inv_std) return null("call->inv_std");
+  if (!c->logp_const) return null("call->logp_const");
+  if (!c->logp_old) return null("call->logp_old");
+  if (!c->advantage) return null("call->advantage");
+  if (grad) {
+    if (!c->grad_scale) return null("call->grad_scale");
+    if (!c->grad_mean && !c->grad_value) return null("call->grad_mean and call->grad_value");
+  } else {
+    if (!c->stats) return null("call->stats");
+    if (!c->workspace) return null("call->workspace");
+  }
+  if ((c->value != nullptr) != (c->returns != nullptr)) {
+    std::snprintf(msg, n, "%s: call->value and call->returns must be given both or neither", fn);
+    return EXCENV_EINVAL;
+  }
+  if (grad && c->grad_value && !c->value) {
+    std::snprintf(msg, n, "%s: call->grad_value needs call->value and call->returns", fn);
+    return EXCENV_EINVAL;
+  }
+  if (int rc = ppo_common_refusal(fn, c->n_actions, dtype, B, K, msg, n)) return rc;
+  if (!(c->clip_eps > 0.0 && c->clip_eps < 1.0)) {
+    std::snprintf(msg, n, "%s: call->clip_eps must lie in (0, 1) (got %g)", fn, c->clip_eps);
+    return EXCENV_EINVAL;
+  }
+  if (!grad) {
+    if (c->max_groups < 0) {
+      std::snprintf(msg, n, "%s: call->max_groups must not be negative (got %d; 0: auto)", fn, c->max_groups);
+      return EXCENV_EINVAL;
+    }
+    const int64_t need = ppo_loss_workspace(B, K, c->max_groups);
+    if (c->workspace_bytes < need || (reinterpret_cast<uintptr_t>(c->workspace) & 7u) != 0) {
+      std::snprintf(msg, n, "%s: needs an 8-byte aligned workspace of %lld bytes (excenv_ppo_loss_workspace_bytes)", fn, (long long)need);
+      return EXCENV_EINVAL;
+    }
+  }
+  return ppo_rows_refusal(fn, c->n_actions, K, msg, n);
 }
 
 }  // namespace excenv

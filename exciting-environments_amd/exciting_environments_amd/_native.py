@@ -34,6 +34,9 @@ POLICY_MAX_LAYERS, POLICY_MAX_WIDTH = 4, 64  # excenv_policy_t: linear layers of
 POLICY_MAX_INPUT = 16  # excenv_policy_param_grad: the widest observation row, 8 + MAX_CONTROL
 PARAM_GRAD_CHAIN = 4096  # samples one working-dtype accumulator of policy_param_grad_kernel sums before it goes to fp64
 PARAM_GRAD_AUTO_GROUPS = 512  # its workgroups with max_groups == 0, at most
+PPO_STATS = 5  # excenv_ppo_loss: n, S_surr, S_vsq, S_kl, S_clip in front of S_gls[A]
+PPO_TILE = 1024  # samples of one tile of the PPO kernels: consecutive environments of one row
+PPO_AUTO_GROUPS = 2048  # workgroups of excenv_ppo_loss with max_groups == 0, at most
 ACT_RELU, ACT_TANH = 0, 1
 ACTIVATIONS = {"relu": ACT_RELU, "tanh": ACT_TANH}
 END_TERMINATED, END_TRUNCATED = 1, 2  # excenv_episode_t.end_mask
@@ -145,6 +148,26 @@ class Gae(ctypes.Structure):
                 ("gamma", ctypes.c_double), ("lambda", ctypes.c_double), ("advantage", ctypes.c_void_p), ("returns", ctypes.c_void_p)]
 
 
+class GaussianLogp(ctypes.Structure):
+    """excenv_gaussian_logp_t: lane-major means and samples, the reciprocal deviations and the constant, and where the
+    log-probabilities go (excenv_gaussian_logp)."""
+
+    _fields_ = [("mean", ctypes.c_void_p), ("sample", ctypes.c_void_p), ("inv_std", ctypes.c_void_p), ("logp_const", ctypes.c_void_p),
+                ("n_actions", ctypes.c_int32), ("logp", ctypes.c_void_p)]
+
+
+class PpoLoss(ctypes.Structure):
+    """excenv_ppo_loss_t: the lane-major rows of a PPO update, the clip range, the sums and workspace of excenv_ppo_loss and the
+    scales and outputs of excenv_ppo_loss_grad."""
+
+    _fields_ = [("mean", ctypes.c_void_p), ("sample", ctypes.c_void_p), ("inv_std", ctypes.c_void_p), ("logp_const", ctypes.c_void_p),
+                ("logp_old", ctypes.c_void_p), ("advantage", ctypes.c_void_p), ("value", ctypes.c_void_p), ("returns", ctypes.c_void_p),
+                ("reset", ctypes.c_void_p), ("adv_norm", ctypes.c_void_p), ("n_actions", ctypes.c_int32), ("max_groups", ctypes.c_int32),
+                ("clip_eps", ctypes.c_double), ("stats", ctypes.c_void_p), ("workspace", ctypes.c_void_p),
+                ("workspace_bytes", ctypes.c_int64), ("grad_scale", ctypes.c_void_p), ("grad_mean", ctypes.c_void_p),
+                ("grad_value", ctypes.c_void_p)]
+
+
 class Episode(ctypes.Structure):
     """excenv_episode_t: the reset rows, the end conditions and the gym / reset outputs of excenv_sim_policy_episodes."""
 
@@ -159,7 +182,7 @@ STRUCTS = {Param: "excenv_param_t", PmsmLut: "excenv_pmsm_lut_t", Props: "excenv
            TrajGym: "excenv_traj_gym_t", Control: "excenv_control_t", Feedback: "excenv_feedback_t",
            FeedbackVjp: "excenv_feedback_vjp_t", Policy: "excenv_policy_t", Episode: "excenv_episode_t",
            PolicyVjp: "excenv_policy_vjp_t", PolicyParamGrad: "excenv_policy_param_grad_t", PolicyEval: "excenv_policy_eval_t",
-           Gae: "excenv_gae_t"}
+           Gae: "excenv_gae_t", GaussianLogp: "excenv_gaussian_logp_t", PpoLoss: "excenv_ppo_loss_t"}
 
 _vp, _ci, _i32, _i64, _cd = ctypes.c_void_p, ctypes.c_int, ctypes.c_int32, ctypes.c_int64, ctypes.c_double
 _STEP = [_ci, _ci, _ci, _i64, _vp, _vp, _cd, _vp, _vp, _vp, _vp]  # env, solver, dtype, B, props, control, tau, in, action, out, obs
@@ -231,6 +254,11 @@ PROTOTYPES = {
     "excenv_policy_eval": (_ci, [_ci, _i64, _i64, _i64, _vp, _vp]),
     # dtype, B, K, call, stream
     "excenv_gae": (_ci, [_ci, _i64, _i64, _vp, _vp]),
+    "excenv_gaussian_logp": (_ci, [_ci, _i64, _i64, _vp, _vp]),
+    # B, K, max_groups
+    "excenv_ppo_loss_workspace_bytes": (_i64, [_i64, _i64, _i32]),
+    "excenv_ppo_loss": (_ci, [_ci, _i64, _i64, _vp, _vp]),
+    "excenv_ppo_loss_grad": (_ci, [_ci, _i64, _i64, _vp, _vp]),
     "excenv_state_from_observation": (_ci, [_ci, _ci, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "excenv_update_ref": (_ci, [_ci, _ci, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
     "excenv_observe": (_ci, [_ci, _ci, _i64, _vp, _vp, _vp, _vp, _vp]),

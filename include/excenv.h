@@ -804,6 +804,87 @@ typedef struct {
 } excenv_gae_t;
 int excenv_gae(int dtype, int64_t B, int64_t K, const excenv_gae_t* call, void* stream);
 
+/* ---- the clipped PPO objective of a diagonal Gaussian policy and its gradients on lane-major rows (additions, same
+ * ABI version: a binder probes for the symbols). Everything is lane-major in the working dtype T: mean and sample [K][A][B]; logp,
+ * logp_old, advantage, value and returns [K][B]; reset bytes [K][B] (non-zero: set) at any byte offset, or NULL for never; A = n_actions
+ * is 1 .. EXCENV_MAX_ACTION. inv_std [A] and logp_const [1] are device arrays in T which the caller computes from log_std (in fp64,
+ * then rounded to T):  inv_std[q] = exp(-log_std[q]),  logp_const = -sum_q log_std[q] - A/2 * log(2 pi),  so the log-probability
+ * holds no transcendental. adv_norm is NULL or a device array T[2] (shift, scale); grad_scale is a device array T[2] (w, wv).
+ * lo = (T)(1 - clip_eps) and hi = (T)(1 + clip_eps), both folded in double. Per sample (n, b), fused multiply-adds in the order written:
+ *   z[q]  = (sample[q] - mean[q]) * inv_std[q]
+ *   logp  = logp_const;  for q = 0 .. A-1:  logp = fma(-0.5 * z[q], z[q], logp)
+ *   d     = logp - logp_old;   r = exp(d)                       (device exp; exp(0) == 1 exactly)
+ *   a     = adv_norm ? (advantage - adv_norm[0]) * adv_norm[1] : advantage
+ *   s1    = r * a;   s2 = min(max(r, lo), hi) * a;   surr = min(s1, s2);   active = !(s2 < s1)
+ *   valid = !reset[n]                                           (reset == NULL: always valid)
+ * excenv_gaussian_logp writes logp [K][B] (the first two lines; one launch of gaussian_logp_kernel): the collection-time pass. The
+ * update runs the same instruction sequence, so an unchanged policy gives d == 0 and r == 1 exactly.
+ * excenv_ppo_loss writes stats, double[EXCENV_PPO_STATS + A] on the device: sums over the valid samples, each term computed in T,
+ * converted to fp64 and added in fp64:
+ *   stats[0] = n = sum 1;   stats[1] = S_surr = sum surr;   stats[2] = S_vsq = sum (value - returns)^2   (0 when value is NULL)
+ *   stats[3] = S_kl = sum ((r - 1) - d);   stats[4] = S_clip = sum [r < lo or r > hi]
+ *   stats[5 + q] = S_gls[q] = sum (active ? -(r * a) : 0) * (z[q] * z[q] - 1)
+ * Two launches on `stream`: ppo_loss_kernel, then ppo_loss_reduce_kernel; no atomics. A sample tile is EXCENV_PPO_TILE consecutive
+ * environments of one row, tile number n * ceil(B / EXCENV_PPO_TILE) + b_tile; with Tn tiles and G = min(Tn, max_groups > 0 ?
+ * max_groups : EXCENV_PPO_AUTO_GROUPS) workgroups of 256 lanes, workgroup g owns the tiles first(g) .. first(g + 1) - 1,
+ * first(g) = g * (Tn / G) + min(g, Tn mod G). Lane l adds the samples 4 l .. 4 l + 3 of a tile in ascending order, tile after tile,
+ * into its own fp64 sums; the workgroup adds its lanes by a fixed tree (within a wave lane l += lane l + 32, 16, 8, 4, 2, 1, then the
+ * waves 0 .. 3 in order) and stores one partial set in the workspace; the second launch adds the G partial sets the same way, lane l
+ * taking the sets l, l + 256, .. in ascending order. The order is a function of (B, K, max_groups) only, never of the device, the
+ * alignment of the arrays or the optional pointers: the same call gives the same bits on every run.
+ *   workspace : excenv_ppo_loss_workspace_bytes(B, K, max_groups) bytes of device memory (G * (EXCENV_PPO_STATS + EXCENV_MAX_ACTION)
+ *               * 8; -1 for a bad argument), 8-byte aligned; needs no initialisation
+ * excenv_ppo_loss_grad writes, with w = grad_scale[0] and wv = grad_scale[1] (one launch of ppo_loss_grad_kernel, no reduction):
+ *   gl            = active ? -(r * a) * w : 0
+ *   grad_mean[q]  = valid ? gl * z[q] * inv_std[q] : 0          ([K][A][B]: the grad_raw operand of excenv_policy_param_grad)
+ *   grad_value    = valid ? wv * (value - returns) : 0          ([K][B])
+ * grad_mean or grad_value may be NULL (not both); grad_value needs value and returns. The selects are selects, not products: an
+ * invalid sample's gradients are exactly 0 and it reaches no sum, whatever its inputs hold; a NaN in a valid sample reaches the sums
+ * and that sample's own gradients only.
+ * All three kernels use 16-byte accesses where B % 4 == 0 and every array of T is 16-byte aligned (the flag bytes as one 4-byte word
+ * where reset is 4-byte aligned), element accesses otherwise, with the same samples on the same lanes either way.
+ * Never allocates or synchronises. B == 0 or K == 0 returns EXCENV_OK without a launch: nothing is written, stats included.
+ * excenv_last_launch() reports "gaussian_logp_kernel", "ppo_loss_kernel", "ppo_loss_grad_kernel". Validated before any HIP call:
+ * EXCENV_ENULL names a missing pointer; EXCENV_EINVAL: value and returns not both or neither, n_actions outside 1 .. 2, dtype, B < 0,
+ * K < 0, a clip_eps that is NaN or outside (0, 1), max_groups < 0, a workspace that is too small or misaligned (with the byte count),
+ * K * n_actions >= 2^31 rows. */
+#define EXCENV_PPO_STATS 5             /* n, S_surr, S_vsq, S_kl, S_clip; S_gls[A] follows */
+#define EXCENV_PPO_TILE 1024           /* samples of one tile: consecutive environments of one row, four to a lane */
+#define EXCENV_PPO_AUTO_GROUPS 2048    /* workgroups of max_groups == 0, at most */
+typedef struct {
+  const void* mean;        /* [K][A][B] */
+  const void* sample;      /* [K][A][B]: the pre-clamp action */
+  const void* inv_std;     /* device T[A] */
+  const void* logp_const;  /* device T[1] */
+  int32_t n_actions;       /* A: 1 .. EXCENV_MAX_ACTION */
+  void* logp;              /* (out) [K][B] */
+} excenv_gaussian_logp_t;
+int excenv_gaussian_logp(int dtype, int64_t B, int64_t K, const excenv_gaussian_logp_t* call, void* stream);
+typedef struct {
+  const void* mean;        /* [K][A][B] */
+  const void* sample;      /* [K][A][B] */
+  const void* inv_std;     /* device T[A] */
+  const void* logp_const;  /* device T[1] */
+  const void* logp_old;    /* [K][B] */
+  const void* advantage;   /* [K][B] */
+  const void* value;       /* [K][B] or NULL (with returns) */
+  const void* returns;     /* [K][B] or NULL (with value) */
+  const uint8_t* reset;    /* [K][B] bytes or NULL (never) */
+  const void* adv_norm;    /* device T[2] (shift, scale) or NULL */
+  int32_t n_actions;       /* A: 1 .. EXCENV_MAX_ACTION */
+  int32_t max_groups;      /* excenv_ppo_loss: 0 auto; > 0: at most this many workgroups */
+  double clip_eps;         /* in (0, 1) */
+  double* stats;           /* excenv_ppo_loss: (out) device double[EXCENV_PPO_STATS + A] */
+  void* workspace;         /* excenv_ppo_loss: excenv_ppo_loss_workspace_bytes bytes of device memory, 8-byte aligned */
+  int64_t workspace_bytes;
+  const void* grad_scale;  /* excenv_ppo_loss_grad: device T[2] (w, wv) */
+  void* grad_mean;         /* excenv_ppo_loss_grad: (out) [K][A][B] or NULL */
+  void* grad_value;        /* excenv_ppo_loss_grad: (out) [K][B] or NULL */
+} excenv_ppo_loss_t;
+int64_t excenv_ppo_loss_workspace_bytes(int64_t B, int64_t K, int32_t max_groups);
+int excenv_ppo_loss(int dtype, int64_t B, int64_t K, const excenv_ppo_loss_t* call, void* stream);
+int excenv_ppo_loss_grad(int dtype, int64_t B, int64_t K, const excenv_ppo_loss_t* call, void* stream);
+
 /* ---- replaces CoreEnvironment.vmap_generate_state_from_observation (core_env.py:689-705; per env e.g.
  * pendulum_env.py:331-364, pmsm_env.py:921-970): obs [B][O + n_control] row-major -> denormalised physical state leaves
  * state_out[S][B] and, for each controlled field control_idx[j], its denormalised reference leaf reference_out[j][B]
