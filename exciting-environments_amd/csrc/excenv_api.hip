@@ -907,6 +907,34 @@ int excenv_ppo_loss_grad(int dtype, int64_t B, int64_t K, const excenv_ppo_loss_
   return launch_ppo_loss(true, dtype, B, K, *call, (hipStream_t)stream);
 }
 
+int64_t excenv_row_moments_workspace_bytes(int64_t B, int64_t N, int32_t n_columns, int32_t max_groups) {
+  if (B < 0 || N < 0 || n_columns < 1 || n_columns > EXCENV_MOMENTS_MAX_COLUMNS || max_groups < 0) return -1;
+  return row_moments_workspace(B, N, n_columns, max_groups);
+}
+
+int excenv_row_moments(int dtype, int64_t B, int64_t N, const excenv_row_moments_t* call, void* stream) {
+  {
+    char why[256];
+    if (int rc = row_moments_refusal(dtype, B, N, call, why, sizeof(why))) { set_error("%s", why); return rc; }
+  }
+  if (B == 0 || N == 0) return EXCENV_OK;
+  return launch_row_moments(dtype, B, N, *call, (hipStream_t)stream);
+}
+
+int64_t excenv_episode_stats_workspace_bytes(int64_t B) {
+  if (B < 0 || episode_stats_groups(B) >= ((int64_t)1 << 31)) return -1;
+  return episode_stats_workspace(B);
+}
+
+int excenv_episode_stats(int dtype, int64_t B, int64_t K, const excenv_episode_stats_t* call, void* stream) {
+  {
+    char why[256];
+    if (int rc = episode_stats_refusal(dtype, B, K, call, why, sizeof(why))) { set_error("%s", why); return rc; }
+  }
+  if (B == 0 || K == 0) return EXCENV_OK;
+  return launch_episode_stats(dtype, B, K, *call, (hipStream_t)stream);
+}
+
 int excenv_state_from_observation(int env, int dtype, int64_t B, const excenv_props_t* props, int32_t n_control,
                                   const int32_t* control_idx, const void* obs, void* const* state_out,
                                   void* const* reference_out, void* stream) {

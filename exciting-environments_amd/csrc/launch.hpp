@@ -720,4 +720,78 @@ template <template <typename> class MT> struct EnvEntry {
   }
 };
 
+// ---- rollout statistics on lane-major rows: excenv_row_moments, excenv_episode_stats --------------------------------
+// row_moments_kernel<T>, episode_stats_kernel<T> and rollout_stats_reduce_kernel (rollout_stats.hip): no model, one instantiation per type
+constexpr const char* row_moments_name() { return "row_moments_kernel"; }
+constexpr const char* episode_stats_name() { return "episode_stats_kernel"; }
+constexpr int STATS_BLOCK = 256;  // four waves: the moments' tiles are the PPO kernels' (PPO_LANE samples a lane), the scan has one environment per lane
+static_assert(STATS_BLOCK == PPO_BLOCK, "a tile of the moments is a PPO tile");
+// Rows of loads a lane of episode_stats_kernel keeps in flight ahead of the scan
+constexpr int EPISODE_DEPTH = 8;
+
+int launch_row_moments(int dtype, int64_t B, int64_t N, const excenv_row_moments_t& call, hipStream_t stream);
+int launch_episode_stats(int dtype, int64_t B, int64_t K, const excenv_episode_stats_t& call, hipStream_t stream);
+
+// One partial set per workgroup: functions of (B, N, C, max_groups) and of B only
+inline int64_t row_moments_workspace(int64_t B, int64_t N, int C, int32_t max_groups) { return ppo_groups(B, N, max_groups) * (1 + 2 * C) * 8; }
+inline int64_t episode_stats_groups(int64_t B) { return (B + STATS_BLOCK - 1) / STATS_BLOCK; }
+inline int64_t episode_stats_workspace(int64_t B) { return episode_stats_groups(B) * EXCENV_EPISODE_STATS * 8; }
+
+// What the two entries refuse: EXCENV_OK, or the code with the message in `msg`. NULL pointers first, then values.
+inline int stats_common_refusal(const char* fn, int dtype, int64_t B, int64_t K, const char* rows, char* msg, size_t n) {
+  if (dtype != EXCENV_F32 && dtype != EXCENV_F64) {
+    std::snprintf(msg, n, "%s: dtype must be EXCENV_F32 (0) or EXCENV_F64 (1) (got %d)", fn, dtype);
+    return EXCENV_EINVAL;
+  }
+  if (B < 0 || K < 0) {
+    std::snprintf(msg, n, "%s: bad B=%lld or %s=%lld", fn, (long long)B, rows, (long long)K);
+    return EXCENV_EINVAL;
+  }
+  return EXCENV_OK;
+}
+inline int stats_workspace_refusal(const char* fn, const void* workspace, int64_t have, int64_t need, char* msg, size_t n) {
+  if (have < need || (reinterpret_cast<uintptr_t>(workspace) & 7u) != 0) {
+    std::snprintf(msg, n, "%s: needs an 8-byte aligned workspace of %lld bytes (%s_workspace_bytes)", fn, (long long)need, fn);
+    return EXCENV_EINVAL;
+  }
+  return EXCENV_OK;
+}
+inline int row_moments_refusal(int dtype, int64_t B, int64_t N, const excenv_row_moments_t* c, char* msg, size_t n) {
+  const char* fn = "excenv_row_moments";
+  auto null = [&](const char* what) { std::snprintf(msg, n, "%s: %s is NULL", fn, what); return EXCENV_ENULL; };
+  if (!c) return null("call");
+  if (!c->x) return null("call->x");
+  if (!c->stats) return null("call->stats");
+  if (!c->workspace) return null("call->workspace");
+  if (int rc = stats_common_refusal(fn, dtype, B, N, "N", msg, n)) return rc;
+  if (c->n_columns < 1 || c->n_columns > EXCENV_MOMENTS_MAX_COLUMNS) {
+    std::snprintf(msg, n, "%s: call->n_columns must be 1 .. %d (got %d)", fn, EXCENV_MOMENTS_MAX_COLUMNS, c->n_columns);
+    return EXCENV_EINVAL;
+  }
+  if (c->max_groups < 0) {
+    std::snprintf(msg, n, "%s: call->max_groups must not be negative (got %d; 0: auto)", fn, c->max_groups);
+    return EXCENV_EINVAL;
+  }
+  if (N > (int64_t)0x7fffffff / c->n_columns) {
+    std::snprintf(msg, n, "%s: N * n_columns = %lld * %d rows exceed one launch", fn, (long long)N, c->n_columns);
+    return EXCENV_EINVAL;
+  }
+  return stats_workspace_refusal(fn, c->workspace, c->workspace_bytes, row_moments_workspace(B, N, c->n_columns, c->max_groups), msg, n);
+}
+inline int episode_stats_refusal(int dtype, int64_t B, int64_t K, const excenv_episode_stats_t* c, char* msg, size_t n) {
+  const char* fn = "excenv_episode_stats";
+  auto null = [&](const char* what) { std::snprintf(msg, n, "%s: %s is NULL", fn, what); return EXCENV_ENULL; };
+  if (!c) return null("call");
+  if (!c->reward) return null("call->reward");
+  if (!c->reset) return null("call->reset");
+  if (!c->stats) return null("call->stats");
+  if (!c->workspace) return null("call->workspace");
+  if (int rc = stats_common_refusal(fn, dtype, B, K, "K", msg, n)) return rc;
+  if (episode_stats_groups(B) >= ((int64_t)1 << 31)) {
+    std::snprintf(msg, n, "%s: batch too large for one launch", fn);
+    return EXCENV_EUNSUPPORTED;
+  }
+  return stats_workspace_refusal(fn, c->workspace, c->workspace_bytes, episode_stats_workspace(B), msg, n);
+}
+
 }  // namespace excenv

@@ -37,6 +37,8 @@ PARAM_GRAD_AUTO_GROUPS = 512  # its workgroups with max_groups == 0, at most
 PPO_STATS = 5  # excenv_ppo_loss: n, S_surr, S_vsq, S_kl, S_clip in front of S_gls[A]
 PPO_TILE = 1024  # samples of one tile of the PPO kernels: consecutive environments of one row
 PPO_AUTO_GROUPS = 2048  # workgroups of excenv_ppo_loss with max_groups == 0, at most
+MOMENTS_MAX_COLUMNS = 16  # excenv_row_moments: the widest row, C
+EPISODE_STATS = 6  # excenv_episode_stats: cnt, SR, SRR, SL, mn, mx
 ACT_RELU, ACT_TANH = 0, 1
 ACTIVATIONS = {"relu": ACT_RELU, "tanh": ACT_TANH}
 END_TERMINATED, END_TRUNCATED = 1, 2  # excenv_episode_t.end_mask
@@ -168,6 +170,23 @@ class PpoLoss(ctypes.Structure):
                 ("grad_value", ctypes.c_void_p)]
 
 
+class RowMoments(ctypes.Structure):
+    """excenv_row_moments_t: lane-major rows, the optional mask bytes and shifts, the sums and the workspace (excenv_row_moments)."""
+
+    _fields_ = [("x", ctypes.c_void_p), ("mask", ctypes.c_void_p), ("shift", ctypes.c_void_p), ("n_columns", ctypes.c_int32),
+                ("max_groups", ctypes.c_int32), ("stats", ctypes.c_void_p), ("workspace", ctypes.c_void_p),
+                ("workspace_bytes", ctypes.c_int64)]
+
+
+class EpisodeStats(ctypes.Structure):
+    """excenv_episode_stats_t: lane-major rewards and reset bytes, the two carries in and out, the per-row returns, the six statistics
+    and the workspace (excenv_episode_stats)."""
+
+    _fields_ = [("reward", ctypes.c_void_p), ("reset", ctypes.c_void_p), ("return_in", ctypes.c_void_p), ("steps_in", ctypes.c_void_p),
+                ("completed", ctypes.c_void_p), ("return_out", ctypes.c_void_p), ("steps_out", ctypes.c_void_p),
+                ("stats", ctypes.c_void_p), ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_int64)]
+
+
 class Episode(ctypes.Structure):
     """excenv_episode_t: the reset rows, the end conditions and the gym / reset outputs of excenv_sim_policy_episodes."""
 
@@ -182,7 +201,8 @@ STRUCTS = {Param: "excenv_param_t", PmsmLut: "excenv_pmsm_lut_t", Props: "excenv
            TrajGym: "excenv_traj_gym_t", Control: "excenv_control_t", Feedback: "excenv_feedback_t",
            FeedbackVjp: "excenv_feedback_vjp_t", Policy: "excenv_policy_t", Episode: "excenv_episode_t",
            PolicyVjp: "excenv_policy_vjp_t", PolicyParamGrad: "excenv_policy_param_grad_t", PolicyEval: "excenv_policy_eval_t",
-           Gae: "excenv_gae_t", GaussianLogp: "excenv_gaussian_logp_t", PpoLoss: "excenv_ppo_loss_t"}
+           Gae: "excenv_gae_t", GaussianLogp: "excenv_gaussian_logp_t", PpoLoss: "excenv_ppo_loss_t",
+           RowMoments: "excenv_row_moments_t", EpisodeStats: "excenv_episode_stats_t"}
 
 _vp, _ci, _i32, _i64, _cd = ctypes.c_void_p, ctypes.c_int, ctypes.c_int32, ctypes.c_int64, ctypes.c_double
 _STEP = [_ci, _ci, _ci, _i64, _vp, _vp, _cd, _vp, _vp, _vp, _vp]  # env, solver, dtype, B, props, control, tau, in, action, out, obs
@@ -259,6 +279,13 @@ PROTOTYPES = {
     "excenv_ppo_loss_workspace_bytes": (_i64, [_i64, _i64, _i32]),
     "excenv_ppo_loss": (_ci, [_ci, _i64, _i64, _vp, _vp]),
     "excenv_ppo_loss_grad": (_ci, [_ci, _i64, _i64, _vp, _vp]),
+    # B, N, n_columns, max_groups
+    "excenv_row_moments_workspace_bytes": (_i64, [_i64, _i64, _i32, _i32]),
+    # dtype, B, N, call, stream
+    "excenv_row_moments": (_ci, [_ci, _i64, _i64, _vp, _vp]),
+    "excenv_episode_stats_workspace_bytes": (_i64, [_i64]),
+    # dtype, B, K, call, stream
+    "excenv_episode_stats": (_ci, [_ci, _i64, _i64, _vp, _vp]),
     "excenv_state_from_observation": (_ci, [_ci, _ci, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "excenv_update_ref": (_ci, [_ci, _ci, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
     "excenv_observe": (_ci, [_ci, _ci, _i64, _vp, _vp, _vp, _vp, _vp]),

@@ -35,6 +35,7 @@ from ._policy import PolicyMixin
 from ._policy_vjp import PolicyVjpMixin
 from ._policy_eval import PolicyEvalMixin
 from ._ppo import PpoMixin
+from ._rollout_stats import RolloutStatsMixin
 from ._linearize import LinearizeMixin
 from ._step_vjp import StepVjpMixin
 from ._vjp import TrajectoryVjpMixin
@@ -53,7 +54,7 @@ def _is_scalar(x) -> bool:
 
 
 class CoreEnvironment(TrajectoryLaunchMixin, TrajectoryVjpMixin, RewardVjpMixin, StepVjpMixin, LinearizeMixin, FeedbackMixin,
-                      FeedbackVjpMixin, PolicyMixin, PolicyVjpMixin, PolicyEvalMixin, PpoMixin, ABC):
+                      FeedbackVjpMixin, PolicyMixin, PolicyVjpMixin, PolicyEvalMixin, PpoMixin, RolloutStatsMixin, ABC):
     """Core structure of the provided environments (reference core_env.py:15-57).
 
     The simulated systems are physical state-space models dx/dt = f(x(t), u(t)); outputs are

@@ -885,6 +885,92 @@ int64_t excenv_ppo_loss_workspace_bytes(int64_t B, int64_t K, int32_t max_groups
 int excenv_ppo_loss(int dtype, int64_t B, int64_t K, const excenv_ppo_loss_t* call, void* stream);
 int excenv_ppo_loss_grad(int dtype, int64_t B, int64_t K, const excenv_ppo_loss_t* call, void* stream);
 
+/* ---- rollout statistics on lane-major rows (additions, same ABI version: a binder probes for the symbols): the
+ * masked column moments a normalisation needs, and the returns and lengths of the episodes a rollout finished. T is the working
+ * dtype; every sum is fp64. No atomics; the same call gives the same bits on every run. Neither entry allocates or synchronises.
+ *
+ * excenv_row_moments: masked column moments of lane-major rows.
+ *   x      : [N][C][B] in T, C = n_columns = 1 .. EXCENV_MOMENTS_MAX_COLUMNS
+ *   mask   : [N][B] bytes at any byte offset, non-zero = sample excluded; or NULL (none excluded)
+ *   shift  : device double[C] or NULL (zeros)
+ *   stats  : (out) device double[1 + 2 C]
+ *   per valid sample (n, b) and column c, all in fp64:
+ *       d = (double)x[n][c][b] - shift[c];   S1[c] += d;   S2[c] += d * d      (the product rounded, then added)
+ *   stats[0] = number of valid samples;  stats[1 + c] = S1[c];  stats[1 + C + c] = S2[c]
+ * The exclusion is a select: an excluded sample reaches no sum whatever it holds, and a NaN in a valid sample reaches the sums of its
+ * own column only. Two launches on `stream`: row_moments_kernel, then rollout_stats_reduce_kernel. The tiles and workgroups are
+ * excenv_ppo_loss's with K = N: a tile is EXCENV_PPO_TILE consecutive environments of one row, tile number n * ceil(B /
+ * EXCENV_PPO_TILE) + b_tile; with Tn tiles and G = min(Tn, max_groups > 0 ? max_groups : EXCENV_PPO_AUTO_GROUPS) workgroups of 256
+ * lanes, workgroup g owns the tiles first(g) .. first(g + 1) - 1, first(g) = g * (Tn / G) + min(g, Tn mod G). Lane l adds the samples
+ * 4 l .. 4 l + 3 of a tile in ascending order, tile after tile, into its own fp64 sums; the workgroup adds its lanes by a fixed tree
+ * (within a wave lane l += lane l + 32, 16, 8, 4, 2, 1, then the waves 0 .. 3 in order) and stores one partial set in the workspace;
+ * the second launch adds the G sets the same way, lane l taking the sets l, l + 256, .. in ascending order. The order is a function of
+ * (B, N, C, max_groups) only. 16-byte accesses where B % 4 == 0 and x is 16-byte aligned (the mask as one 4-byte word where B % 4 == 0
+ * and it is 4-byte aligned), element accesses otherwise, with the same samples on the same lanes either way.
+ *   workspace : excenv_row_moments_workspace_bytes(B, N, C, max_groups) bytes of device memory (G * (1 + 2 C) * 8; -1 for a bad
+ *               argument), 8-byte aligned; needs no initialisation
+ * B == 0 or N == 0 returns EXCENV_OK without a launch: nothing is written, stats included. excenv_last_launch() reports
+ * "row_moments_kernel". Validated before any HIP call: EXCENV_ENULL names a missing pointer (call, x, stats, workspace);
+ * EXCENV_EINVAL: dtype, B < 0, N < 0, n_columns out of range, max_groups < 0, a workspace that is too small or misaligned (with the
+ * byte count), N * n_columns >= 2^31 rows. */
+#define EXCENV_MOMENTS_MAX_COLUMNS 16
+typedef struct {
+  const void* x;           /* [N][C][B] */
+  const uint8_t* mask;     /* [N][B] bytes or NULL (none excluded) */
+  const double* shift;     /* device double[C] or NULL (zeros) */
+  int32_t n_columns;       /* C: 1 .. EXCENV_MOMENTS_MAX_COLUMNS */
+  int32_t max_groups;      /* 0 auto; > 0: at most this many workgroups */
+  double* stats;           /* (out) device double[1 + 2 C] */
+  void* workspace;         /* excenv_row_moments_workspace_bytes bytes of device memory, 8-byte aligned */
+  int64_t workspace_bytes;
+} excenv_row_moments_t;
+int64_t excenv_row_moments_workspace_bytes(int64_t B, int64_t N, int32_t n_columns, int32_t max_groups);
+int excenv_row_moments(int dtype, int64_t B, int64_t N, const excenv_row_moments_t* call, void* stream);
+
+/* excenv_episode_stats: returns and lengths of the episodes a rollout finished, in the convention of excenv_sim_policy_episodes:
+ * reward[n] belongs to row n + 1; reset[n] != 0 says the episode ended at row n and transition n is no step, so its reward is dropped.
+ * Per environment b:
+ *   ret = return_in[b] (double; 0 where NULL);   len = steps_in[b] (int32; 0 where NULL)
+ *   for n = 0 .. K-1:
+ *       if reset[n]:
+ *           if len > 0:  emit (ret, len);  completed[n][b] = ret   else: completed[n][b] = 0
+ *           ret = 0;  len = 0
+ *       else:
+ *           ret = ret + (double)reward[n];  len += 1;  completed[n][b] = 0
+ *   return_out[b] = ret;  steps_out[b] = len
+ *   emit(R, L):  cnt += 1;  SR += R;  SRR += R * R;  SL += L;  mn = R < mn ? R : mn;  mx = R > mx ? R : mx
+ *   stats = double[EXCENV_EPISODE_STATS]: cnt, SR, SRR, SL, mn (+inf when cnt == 0), mx (-inf)
+ * An episode with no transition is not an episode (a reset state that is itself terminal; every step a reset). The comparisons are as
+ * written, so a NaN return is never selected as min or max. A NaN in a dropped reward changes no bit anywhere; a NaN in a counted
+ * reward reaches that environment's ret, its completed entry, SR and SRR, and nothing else. With the episode_steps_in a rollout was
+ * given, steps_out is its episode_steps_out.
+ *   reward [K][B] in T;  reset [K][B] bytes at any byte offset, required;  return_in double[B], steps_in int32[B]: or NULL
+ *   completed (out) double [K][B], return_out (out) double[B], steps_out (out) int32[B]: each may be NULL;  stats (out) double[6]
+ * Two launches on `stream`: episode_stats_kernel, one environment per lane in workgroups of 256 lanes with the loads of
+ * several rows in flight ahead of the scan, each environment adding its episodes in row order into its own six values; the workgroup
+ * combines its lanes by the fixed tree above (min and max by the same tree with the comparisons as written) into one partial set of
+ * the workspace; rollout_stats_reduce_kernel combines the ceil(B / 256) sets the same way. The order is a function of B only.
+ *   workspace : excenv_episode_stats_workspace_bytes(B) bytes of device memory (ceil(B / 256) * EXCENV_EPISODE_STATS * 8; -1 for a bad
+ *               argument), 8-byte aligned; needs no initialisation
+ * B == 0 or K == 0 returns EXCENV_OK without a launch: nothing is written. excenv_last_launch() reports "episode_stats_kernel".
+ * Validated before any HIP call: EXCENV_ENULL names a missing pointer (call, reward, reset, stats, workspace); EXCENV_EINVAL: dtype,
+ * B < 0, K < 0, a workspace that is too small or misaligned (with the byte count); EXCENV_EUNSUPPORTED: a batch of 2^39 or more. */
+#define EXCENV_EPISODE_STATS 6         /* cnt, SR, SRR, SL, mn, mx */
+typedef struct {
+  const void* reward;       /* [K][B] */
+  const uint8_t* reset;     /* [K][B] bytes */
+  const double* return_in;  /* [B] or NULL (zeros) */
+  const int32_t* steps_in;  /* [B] or NULL (zeros) */
+  double* completed;        /* (out) [K][B] or NULL */
+  double* return_out;       /* (out) [B] or NULL */
+  int32_t* steps_out;       /* (out) [B] or NULL */
+  double* stats;            /* (out) device double[EXCENV_EPISODE_STATS] */
+  void* workspace;          /* excenv_episode_stats_workspace_bytes bytes of device memory, 8-byte aligned */
+  int64_t workspace_bytes;
+} excenv_episode_stats_t;
+int64_t excenv_episode_stats_workspace_bytes(int64_t B);
+int excenv_episode_stats(int dtype, int64_t B, int64_t K, const excenv_episode_stats_t* call, void* stream);
+
 /* ---- replaces CoreEnvironment.vmap_generate_state_from_observation (core_env.py:689-705; per env e.g.
  * pendulum_env.py:331-364, pmsm_env.py:921-970): obs [B][O + n_control] row-major -> denormalised physical state leaves
  * state_out[S][B] and, for each controlled field control_idx[j], its denormalised reference leaf reference_out[j][B]
