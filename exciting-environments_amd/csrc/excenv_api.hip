@@ -6,6 +6,7 @@
 #include <cstdio>
 #include <dlfcn.h>
 #include "launch.hpp"
+#include "riccati.hpp"
 
 static_assert(EXCENV_FAULT == 0, "EXCENV_FAULT builds exist for tools/isa_guards_selftest.sh only (single objects, never linked into the library)");
 
@@ -933,6 +934,20 @@ int excenv_episode_stats(int dtype, int64_t B, int64_t K, const excenv_episode_s
   }
   if (B == 0 || K == 0) return EXCENV_OK;
   return launch_episode_stats(dtype, B, K, *call, (hipStream_t)stream);
+}
+
+int excenv_lqr_backward(int dtype, int64_t B, int64_t N, const excenv_lqr_t* call, void* stream) {
+  {
+    char why[256];
+    if (int rc = riccati_refusal(dtype, B, N, call, why, sizeof(why))) { set_error("%s", why); return rc; }
+  }
+  if (B == 0) return EXCENV_OK;
+  return launch_riccati(dtype, B, N, *call, (hipStream_t)stream);
+}
+
+int64_t excenv_lqr_backward_bytes(int dtype, int32_t n_state, int32_t n_action, int time_invariant, int has_q, int has_r, int store_all,
+                                  int has_ff) {
+  return riccati_bytes(dtype, n_state, n_action, time_invariant, has_q, has_r, store_all, has_ff);
 }
 
 int excenv_state_from_observation(int env, int dtype, int64_t B, const excenv_props_t* props, int32_t n_control,

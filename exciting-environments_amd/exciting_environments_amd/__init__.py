@@ -15,6 +15,7 @@ from .registration import EnvironmentRegistry
 from .gym_wrapper import GymWrapper
 from ._policy import MLPPolicy
 from ._ppo import PpoLoss
+from ._lqr import LQRSolution
 from ._rollout_stats import EpisodeStats, RowMoments, RunningMoments
 from .solvers import Euler, RK4, Tsit5
 from .stepper import Stepper
@@ -23,6 +24,6 @@ from . import random, tree, utils
 
 __all__ = [
     "CoreEnvironment", "Acrobot", "CartPole", "FluidTank", "MassSpringDamper", "Pendulum", "PMSM", "MotorVariant", "prepare_pmsm_lut", "load_pmsm_lut",
-    "EnvironmentRegistry", "GymWrapper", "MLPPolicy", "PpoLoss", "RowMoments", "EpisodeStats", "RunningMoments", "Stepper", "Euler", "RK4", "Tsit5", "MinMaxNormalization", "dump_sim_properties_to_json",
+    "EnvironmentRegistry", "GymWrapper", "MLPPolicy", "PpoLoss", "RowMoments", "EpisodeStats", "RunningMoments", "LQRSolution", "Stepper", "Euler", "RK4", "Tsit5", "MinMaxNormalization", "dump_sim_properties_to_json",
     "load_sim_properties_from_json", "random", "tree", "utils",
 ]

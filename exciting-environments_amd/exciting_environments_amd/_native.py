@@ -39,6 +39,7 @@ PPO_TILE = 1024  # samples of one tile of the PPO kernels: consecutive environme
 PPO_AUTO_GROUPS = 2048  # workgroups of excenv_ppo_loss with max_groups == 0, at most
 MOMENTS_MAX_COLUMNS = 16  # excenv_row_moments: the widest row, C
 EPISODE_STATS = 6  # excenv_episode_stats: cnt, SR, SRR, SL, mn, mx
+LQR_SHAPES = ((1, 1), (2, 1), (4, 1), (7, 2))  # excenv_lqr_backward: the (n_state, n_action) riccati_kernel is instantiated for
 ACT_RELU, ACT_TANH = 0, 1
 ACTIVATIONS = {"relu": ACT_RELU, "tanh": ACT_TANH}
 END_TERMINATED, END_TRUNCATED = 1, 2  # excenv_episode_t.end_mask
@@ -187,6 +188,16 @@ class EpisodeStats(ctypes.Structure):
                 ("stats", ctypes.c_void_p), ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_int64)]
 
 
+class Lqr(ctypes.Structure):
+    """excenv_lqr_t: the stored Jacobians, the cost matrices and linear terms, and the outputs of the Riccati recursion
+    (excenv_lqr_backward)."""
+
+    _fields_ = [("n_state", ctypes.c_int32), ("n_action", ctypes.c_int32), ("jac", ctypes.c_void_p), ("jac_row_stride", ctypes.c_int64),
+                ("Q", ctypes.c_void_p), ("Qf", ctypes.c_void_p), ("R", ctypes.c_void_p), ("q", ctypes.c_void_p), ("r", ctypes.c_void_p),
+                ("reg", ctypes.c_double), ("store_all", ctypes.c_int32), ("gain", ctypes.c_void_p), ("ff", ctypes.c_void_p),
+                ("P0", ctypes.c_void_p), ("p0", ctypes.c_void_p), ("dV", ctypes.c_void_p), ("n_bad", ctypes.c_void_p)]
+
+
 class Episode(ctypes.Structure):
     """excenv_episode_t: the reset rows, the end conditions and the gym / reset outputs of excenv_sim_policy_episodes."""
 
@@ -202,7 +213,7 @@ STRUCTS = {Param: "excenv_param_t", PmsmLut: "excenv_pmsm_lut_t", Props: "excenv
            FeedbackVjp: "excenv_feedback_vjp_t", Policy: "excenv_policy_t", Episode: "excenv_episode_t",
            PolicyVjp: "excenv_policy_vjp_t", PolicyParamGrad: "excenv_policy_param_grad_t", PolicyEval: "excenv_policy_eval_t",
            Gae: "excenv_gae_t", GaussianLogp: "excenv_gaussian_logp_t", PpoLoss: "excenv_ppo_loss_t",
-           RowMoments: "excenv_row_moments_t", EpisodeStats: "excenv_episode_stats_t"}
+           RowMoments: "excenv_row_moments_t", EpisodeStats: "excenv_episode_stats_t", Lqr: "excenv_lqr_t"}
 
 _vp, _ci, _i32, _i64, _cd = ctypes.c_void_p, ctypes.c_int, ctypes.c_int32, ctypes.c_int64, ctypes.c_double
 _STEP = [_ci, _ci, _ci, _i64, _vp, _vp, _cd, _vp, _vp, _vp, _vp]  # env, solver, dtype, B, props, control, tau, in, action, out, obs
@@ -286,6 +297,10 @@ PROTOTYPES = {
     "excenv_episode_stats_workspace_bytes": (_i64, [_i64]),
     # dtype, B, K, call, stream
     "excenv_episode_stats": (_ci, [_ci, _i64, _i64, _vp, _vp]),
+    # dtype, B, N, call, stream
+    "excenv_lqr_backward": (_ci, [_ci, _i64, _i64, _vp, _vp]),
+    # dtype, n_state, n_action, time_invariant, has_q, has_r, store_all, has_ff
+    "excenv_lqr_backward_bytes": (_i64, [_ci, _i32, _i32, _ci, _ci, _ci, _ci, _ci]),
     "excenv_state_from_observation": (_ci, [_ci, _ci, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "excenv_update_ref": (_ci, [_ci, _ci, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
     "excenv_observe": (_ci, [_ci, _ci, _i64, _vp, _vp, _vp, _vp, _vp]),

@@ -37,6 +37,7 @@ from ._policy_eval import PolicyEvalMixin
 from ._ppo import PpoMixin
 from ._rollout_stats import RolloutStatsMixin
 from ._linearize import LinearizeMixin
+from ._lqr import LqrMixin
 from ._step_vjp import StepVjpMixin
 from ._vjp import TrajectoryVjpMixin
 from .solvers import Euler, _Solver
@@ -54,7 +55,7 @@ def _is_scalar(x) -> bool:
 
 
 class CoreEnvironment(TrajectoryLaunchMixin, TrajectoryVjpMixin, RewardVjpMixin, StepVjpMixin, LinearizeMixin, FeedbackMixin,
-                      FeedbackVjpMixin, PolicyMixin, PolicyVjpMixin, PolicyEvalMixin, PpoMixin, RolloutStatsMixin, ABC):
+                      FeedbackVjpMixin, PolicyMixin, PolicyVjpMixin, PolicyEvalMixin, PpoMixin, RolloutStatsMixin, LqrMixin, ABC):
     """Core structure of the provided environments (reference core_env.py:15-57).
 
     The simulated systems are physical state-space models dx/dt = f(x(t), u(t)); outputs are

@@ -971,6 +971,78 @@ typedef struct {
 int64_t excenv_episode_stats_workspace_bytes(int64_t B);
 int excenv_episode_stats(int dtype, int64_t B, int64_t K, const excenv_episode_stats_t* call, void* stream);
 
+/* ---- batched LQR synthesis: the Riccati recursion on stored linearisations (an addition, same ABI version: a binder
+ * probes for the symbol). The backward pass of finite-horizon LQR, which is also the backward pass of iLQR, per environment over N rows
+ * of discrete-time Jacobians. Model-free: S = n_state and A = n_action are the caller's, (S, A) one of (1, 1), (2, 1), (4, 1), (7, 2);
+ * any other shape is EXCENV_EUNSUPPORTED. Everything is lane-major in the working dtype T:
+ *   jac    : [N][S][S + A][B] with jac_row_stride elements between rows; element (n, i, c, b) is F_n[i][c] for c < S and G_n[i][c - S]
+ *            otherwise (x+ = F_n x + G_n u): the allocation excenv_step_jacobian writes for EXCENV_JAC_STATE rows, read in place.
+ *            jac_row_stride == 0: one [S][S + A][B] block read for every row (the time-invariant problem iterated N times)
+ *   Q, Qf  : device T[S][S] shared by every environment and row; Qf == NULL means Q.  R : device T[A][A], likewise. All three are taken
+ *            as symmetric: only the elements [i][j] with i <= j are read
+ *   q      : [N + 1][S][B] or NULL (zeros);  r : [N][A][B] or NULL (zeros): the linear cost terms
+ *   reg    : >= 0, added as (T)reg to the diagonal of Quu for the solve only
+ *   store_all : 1: gain and ff have N rows; 0: one row, that of n = 0 (the stationary use)
+ *   gain   : (out) [N or 1][A][S][B], required;  ff : (out) [N or 1][A][B];  P0 : (out) [S][S][B];  p0 : (out) [S][B];
+ *            dV : (out) [2][B];  n_bad : (out) int32 [B]; each but gain may be NULL
+ * Per environment b, in T, with -ffp-contract=off: every sum runs in ascending index order, a fused multiply-add appears exactly where
+ * `fma` is written, `*` `+` `-` `/` are the plain rounded operations, and "s = c; k: s = fma(x_k, y_k, s)" means the chain over
+ * k = 0 .. S-1 (a: over a = 0 .. A-1) in ascending order starting from c; "s = x_0 * y_0; k >= 1: ..." starts from the rounded product.
+ *   P[i][j] = Qf[min(i,j)][max(i,j)];  p[i] = q[N][i];  dV0 = dV1 = 0;  bad = 0
+ *   for n = N-1 down to 0, F = F_n, G = G_n:
+ *       W[i][j]   = P[i][0] * F[0][j];   k >= 1: W[i][j]  = fma(P[i][k], F[k][j], W[i][j])             (W = P F)
+ *       Wb[i][a]  = P[i][0] * G[0][a];   k >= 1: Wb[i][a] = fma(P[i][k], G[k][a], Wb[i][a])            (Wb = P G)
+ *       Qxx[i][j] = Q[i][j];             k: Qxx[i][j] = fma(F[k][i], W[k][j], Qxx[i][j])               (i <= j only)
+ *       Qux[a][j] = G[0][a] * W[0][j];   k >= 1: Qux[a][j] = fma(G[k][a], W[k][j], Qux[a][j])
+ *       Quu[a][c] = R[a][c];             k: Quu[a][c] = fma(G[k][a], Wb[k][c], Quu[a][c])              (a <= c only; Quu[1][0] = Quu[0][1])
+ *       Qx[i]     = q[n][i];             k: Qx[i] = fma(F[k][i], p[k], Qx[i])
+ *       Qu[a]     = r[n][a];             k: Qu[a] = fma(G[k][a], p[k], Qu[a])
+ *       solve (Quu + reg I) [K | k] = -[Qux | Qu] by LDL^T without square roots; for each right-hand column g (g = -Qux[.][j] -> K[.][j],
+ *       g = -Qu -> k):
+ *         A = 1:  d0 = Quu[0][0] + reg;  ok = d0 > 0;  x0 = g0 / d0
+ *         A = 2:  d0 = Quu[0][0] + reg;  l = Quu[0][1] / d0;  d1 = fma(-l, Quu[0][1], Quu[1][1] + reg);  ok = d0 > 0 && d1 > 0
+ *                 y1 = fma(-l, g0, g1);  x1 = y1 / d1;  x0 = fma(-l, x1, g0 / d0)
+ *       if !ok:  K = 0, k = 0, bad += 1          (a select, a NaN compares false: the step is then open loop)
+ *       QK[a][j]  = Quu[a][0] * K[0][j];   A = 2: QK[a][j] = fma(Quu[a][1], K[1][j], QK[a][j])         (the unregularised Quu)
+ *       Qk[a]     = Quu[a][0] * k[0];      A = 2: Qk[a]    = fma(Quu[a][1], k[1], Qk[a])
+ *       P[i][j]   = Qxx[i][j];  a: P[i][j] = fma(K[a][i], QK[a][j], P[i][j]);  a: P[i][j] = fma(K[a][i], Qux[a][j], P[i][j]);
+ *                   a: P[i][j] = fma(Qux[a][i], K[a][j], P[i][j])                                      (i <= j; P[j][i] = P[i][j])
+ *       p[i]      = Qx[i];  a: p[i] = fma(K[a][i], Qk[a], p[i]);  a: p[i] = fma(K[a][i], Qu[a], p[i]);  a: p[i] = fma(Qux[a][i], k[a], p[i])
+ *       a: dV0 = fma(k[a], Qu[a], dV0);   h = k[0] * Qk[0];  A = 2: h = fma(k[1], Qk[1], h);   dV1 = dV1 + 0.5 * h
+ *       gain[n] = K;  ff[n] = k           (store_all == 0: row 0 of gain and ff, written at n = 0 only)
+ *   P0 = P;  p0 = p;  dV = (dV0, dV1);  n_bad = bad
+ * So P = Qxx + K^T Quu K + K^T Qux + Qux^T K and p = Qx + K^T Quu k + K^T Qu + Qux^T k, dV0 = sum_n k . Qu and dV1 = 1/2 sum_n k . Quu k:
+ * the two numbers of an iLQR line search. An environment's values reach no other environment.
+ * One launch of riccati_kernel on `stream`: one environment per lane in workgroups of 256 lanes, every access one element per lane
+ * and coalesced along the batch; no atomics, no reduction across lanes: the same call gives the same bits on every run. Never
+ * allocates or synchronises. B == 0 returns EXCENV_OK without a launch; N == 0 writes P0 = Qf, p0 = q[0], dV = 0, n_bad = 0 and no row of
+ * gain or ff. excenv_last_launch() reports "riccati_kernel". Validated before any HIP call: EXCENV_ENULL names a missing pointer (call,
+ * jac, Q, R, gain); EXCENV_EINVAL: dtype, B < 0, N < 0, a reg that is negative or NaN, store_all outside 0 / 1, a jac_row_stride that
+ * is neither 0 nor >= S (S + A) B; EXCENV_EUNSUPPORTED: a shape without an instantiation, a batch of 2^39 or more.
+ * excenv_lqr_backward_bytes: the algorithmic bytes per environment and row of such a call (the Jacobian row unless time_invariant, the
+ * q and r rows where given, the gain and ff rows where store_all); -1 for a bad argument. */
+typedef struct {
+  int32_t n_state, n_action;  /* S, A */
+  const void* jac;            /* [N][S][S + A][B], jac_row_stride elements between rows */
+  int64_t jac_row_stride;     /* 0 (one block for every row) or >= S (S + A) B */
+  const void* Q;              /* device T[S][S] */
+  const void* Qf;             /* device T[S][S] or NULL (Q) */
+  const void* R;              /* device T[A][A] */
+  const void* q;              /* [N + 1][S][B] or NULL (zeros) */
+  const void* r;              /* [N][A][B] or NULL (zeros) */
+  double reg;                 /* >= 0 */
+  int32_t store_all;          /* 1: every row of gain and ff; 0: row 0 only */
+  void* gain;                 /* (out) [N or 1][A][S][B] */
+  void* ff;                   /* (out) [N or 1][A][B] or NULL */
+  void* P0;                   /* (out) [S][S][B] or NULL */
+  void* p0;                   /* (out) [S][B] or NULL */
+  void* dV;                   /* (out) [2][B] or NULL */
+  int32_t* n_bad;             /* (out) [B] or NULL */
+} excenv_lqr_t;
+int excenv_lqr_backward(int dtype, int64_t B, int64_t N, const excenv_lqr_t* call, void* stream);
+int64_t excenv_lqr_backward_bytes(int dtype, int32_t n_state, int32_t n_action, int time_invariant, int has_q, int has_r, int store_all,
+                                  int has_ff);
+
 /* ---- replaces CoreEnvironment.vmap_generate_state_from_observation (core_env.py:689-705; per env e.g.
  * pendulum_env.py:331-364, pmsm_env.py:921-970): obs [B][O + n_control] row-major -> denormalised physical state leaves
  * state_out[S][B] and, for each controlled field control_idx[j], its denormalised reference leaf reference_out[j][B]
